@@ -1,7 +1,7 @@
 """Benchmark: SIREN fitting throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config m|c1|c2|c3|c4|c4_fp32|m_fp32|m_shard8]
-                    [--scaling weak|strong] [--precision bf16|fp32] [--no-graph]
+                    [--scaling weak|strong] [--precision bf16|fp32] [--no-graph] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -35,11 +35,24 @@ faster for the 512^2 step on ROCm 7 (graph kernel nodes add a few us each). The 
 kernel's launches are bracketed by HIP event pairs on its launch stream in the eager region (ROCm
 reports no elapsed time between events recorded inside a graph).
 
-Prints ONE JSON line on rank 0: value (coord-samples/s, whole job), roofline of the dominant
-kernel (MFMA-bound per SURVEY.md §8(d): algorithmic FLOPs per launch / launch time / dense peak;
-PMC HBM traffic from profiles/pmc_traffic.json), the step's FLOP roofline, cpu_baseline (the CPU
+A hipGraph holds at most GRAPH_CHUNK captured steps: a longer graph region replays that graph
+K // GRAPH_CHUNK times back to back, then one graph of the remaining steps (instantiating a graph of
+thousands of steps would take longer than running them).
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints
+ONE JSON line on rank 0: value (coord-samples/s, whole job), ms_per_step and the step's FLOP
+roofline (arithmetic on the step time). --dump-outputs DIR writes what the last timed step (the
+eager region's, which runs last whatever --timing reports) computed (its loss, the model output
+and the parameters after its Adam update) as DIR/<name>.npy,
+float32 or float64; an array above its share of 64 MB is a fixed seeded sample. The inputs and the
+number of steps run before the dump depend on the arguments only.
+
+--full adds the legs that take runs of their own: the roofline of the dominant kernel (MFMA-bound
+per SURVEY.md §8(d): algorithmic FLOPs per launch / launch time / dense peak; PMC HBM traffic from
+profiles/pmc_traffic.json), fused_sine_gemm, the C4 encoder's own timing, cpu_baseline (the CPU
 oracle on this host, rank 0, N=1 only), psnr (M: 64^2 cameraman, 500 steps vs the reference's
-golden trajectory) and, for the default run, short measurements of configs c1..c4 ("configs").
+golden trajectory) and, for config m, short measurements of configs c1..c4 ("configs"). The
+--no-* options switch single legs of a --full run off.
 """
 from __future__ import annotations
 
@@ -94,6 +107,8 @@ KCLASS_SYMBOL = {
 }
 CONFIG_DEFAULT_STEPS = {"m": (50, 10), "c1": (50, 10), "c2": (50, 10), "c3": (20, 5), "c4": (10, 3), "c4_fp32": (5, 2),
                         "m_fp32": (10, 3), "m_shard8": (50, 10)}
+GRAPH_CHUNK = 200      # most steps captured into one hipGraph (see the docstring)
+DUMP_BYTES = 64 << 20  # --dump-outputs: upper bound of everything written
 C4 = dict(num_fourier_features=8, kl_weight=2.78e-8, fw_weight=6.4e-6, lr=5.57e-5, fourier_features_scale=21,
           latent_dim=128, hidden_features_hyper=128, hidden_layers_hyper=2, hidden_layers=3, hidden_features=256,
           conv_kernel_size=7, num_conv_res_blocks=5, w0=30, slices=32, res=128)
@@ -112,9 +127,14 @@ def parse():
                    help="timed region: a hipGraph replay of K captured steps, K eager steps, or (auto) both, "
                         "reporting the faster")
     p.add_argument("--no-graph", action="store_true", help="same as --timing eager")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-psnr", action="store_true")
-    p.add_argument("--no-other-configs", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: dominant-kernel roofline, fused_sine_gemm, "
+                        "encoder timing, PSNR check, the other configs, CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    p.add_argument("--no-psnr", action="store_true", help="--full without the PSNR check")
+    p.add_argument("--no-other-configs", action="store_true", help="--full without the other configs")
     p.add_argument("--cpu-budget-s", type=float, default=12.0, help="CPU seconds per config of the CPU baseline")
     a = p.parse_args()
     st, wu = CONFIG_DEFAULT_STEPS[a.config]
@@ -161,7 +181,8 @@ def encoder_flops_fwd(k, res_blocks, latent, res):
 # ------------------------------------------------------------------------------ workloads
 class Workload:
     """step(): one training step; coords: coordinate samples per rank per step; flops: algorithmic
-    FLOPs per rank per step of the SIREN (encoder separately); kdims: the SIREN dims."""
+    FLOPs per rank per step of the SIREN (encoder separately); kdims: the SIREN dims. extra["last"]:
+    the loss and model output of the most recent step (references, for --dump-outputs)."""
 
     def __init__(self, name, step, coords, flops, dims, precision, workload, data, extra=None):
         self.name, self.step, self.coords, self.flops, self.dims = name, step, coords, flops, dims
@@ -201,6 +222,7 @@ def build_fit(cfg, args, dev, rank, world, precision, shard_of=None):
     reducer = GradAllReducer(model.parameters(), op="sum") if world > 1 else None
     model_input = {"coords": coords}
     one = torch.ones((), device=dev)  # the backward's seed, allocated once (not a fill kernel per step)
+    last = {}
 
     def step():
         # training.train's step: the target staged for the forward's fused loss epilogue
@@ -211,6 +233,7 @@ def build_fit(cfg, args, dev, rank, world, precision, shard_of=None):
         out = model(model_input)
         loss = loss_functions.weighted_sse(out["model_out"], tgt)
         fusion.clear(st)
+        last["model_out"], last["loss"] = out["model_out"].detach(), loss.detach()
         loss.backward(one)
         if reducer is not None:
             reducer()
@@ -225,7 +248,7 @@ def build_fit(cfg, args, dev, rank, world, precision, shard_of=None):
           f"{' (1/' + str(shard_of) + ' shard, no exchange)' if shard_of else ''}, "
           f"SingleBVPNet {'-'.join(map(str, dims))} (w0=30), image_mse + Adam(1e-4), full batch")
     return Workload(cfg, step, n, 3 * siren_fwd_flops(dims) * n, dims, precision, wl, data,
-                    {"optimizer": opt, "side": side})
+                    {"optimizer": opt, "side": side, "last": last})
 
 
 def build_c3(args, dev, rank, world, precision):
@@ -243,10 +266,12 @@ def build_c3(args, dev, rank, world, precision):
     opt = training.make_adam(model.parameters(), 1e-4)
     reducer = GradAllReducer(model.parameters(), op="mean") if world > 1 else None
     model_input = {"coords": coords}
+    last = {}
 
     def step():
         out = model(model_input)
         loss = loss_functions.gradients_mse(out, gtg)["gradients_loss"]
+        last["model_out"], last["loss"] = out["model_out"].detach(), loss.detach()
         loss.backward()
         if reducer is not None:
             reducer()
@@ -260,7 +285,7 @@ def build_c3(args, dev, rank, world, precision):
                     f"train_poisson_grad_img.py-style fit step: {side}x{side} grid, SingleBVPNet 5x256, "
                     "gradients_mse (analytic gradient + its double backward) + Adam(1e-4)",
                     "cameraman 512^2, gt gradients = sobel(10 img) along axes 1, 2 (dataio.py:779-782)",
-                    {"optimizer": opt})
+                    {"optimizer": opt, "last": last})
 
 
 def c4_batch(dev, n_slices, seed=0):
@@ -299,6 +324,7 @@ def build_c4(args, dev, rank, world, precision, encoder_precision="bf16"):
     opt = training.make_adam(model.parameters(), C4["lr"])
     reducer = GradAllReducer(model.parameters(), op="mean") if world > 1 else None
     params = [p for p in model.parameters() if p.requires_grad]
+    last = {}
 
     def step():
         # training.train's transform step: raw coordinates + B for the hypernetwork, whose SIREN forms
@@ -309,6 +335,7 @@ def build_c4(args, dev, rank, world, precision, encoder_precision="bf16"):
         losses = loss_fn(out, gt)
         fusion.clear(st)
         loss = sum(v.mean() for v in losses.values())
+        last["model_out"], last["loss"] = out["model_out"].detach(), loss.detach()
         if reducer is not None:
             reducer.begin()
         loss.backward()
@@ -330,7 +357,7 @@ def build_c4(args, dev, rank, world, precision, encoder_precision="bf16"):
                     "synthetic k-space (IRData slices x flips/rotations + seeded ellipses, fftshift(fft2)), "
                     "seeded CS-Cartesian masks, FF B = randn(2, 8) * 21 (seed 0)",
                     {"optimizer": opt, "encoder_flops_per_step": enc, "encoder_precision": encoder_precision,
-                     "model": model, "inp": inp, "ff": ff, "loss_fn": loss_fn,
+                     "model": model, "inp": inp, "ff": ff, "loss_fn": loss_fn, "last": last,
                      "conv_algorithms": ("MIOpen find (torch.backends.cudnn.benchmark)" if encoder_precision == "bf16"
                                          else "MIOpen immediate mode")})
 
@@ -396,7 +423,7 @@ def run_timed(wl, args, dev, world, kclass=None, max_launches=4096):
     during which the dominant kernel class (kclass) is timed by HIP event pairs on its launch
     stream around each launch (ROCm reports no elapsed time between events recorded inside a
     graph). Returns (elapsed_s of the reported region, region name, KernelTimer or None,
-    {region: elapsed_s})."""
+    {region: elapsed_s}, outputs of the last timed step or None)."""
     from siren_mri_amd import _native
     for _ in range(args.warmup):
         wl.step()
@@ -410,9 +437,17 @@ def run_timed(wl, args, dev, world, kclass=None, max_launches=4096):
             for _ in range(2):
                 g1.replay()
             torch.cuda.synchronize()
-            gk = capture(wl.step, args.steps)
-            regions["graph"] = timed(gk.replay, world)
-            del gk, g1
+            q, r = divmod(args.steps, GRAPH_CHUNK)
+            gq = capture(wl.step, GRAPH_CHUNK) if q else None
+            gr = capture(wl.step, r) if r else None
+
+            def replay():
+                for _ in range(q):
+                    gq.replay()
+                if gr is not None:
+                    gr.replay()
+            regions["graph"] = timed(replay, world)
+            del gq, gr, g1
         except Exception as e:  # noqa: BLE001 - reported, then timed eagerly
             print(f"bench: hipGraph capture failed ({type(e).__name__}: {e}); timing eager steps", file=sys.stderr)
             opt = wl.extra.get("optimizer")
@@ -431,13 +466,40 @@ def run_timed(wl, args, dev, world, kclass=None, max_launches=4096):
         for _ in range(args.steps):
             wl.step()
     regions["eager"] = timed(loop, world)
+    # the eager region always runs last: its last step is the one --dump-outputs writes
+    outputs = last_outputs(wl) if args.dump_outputs else None
     if kt is not None:
         kt.__exit__(None, None, None)
     # the same choice on every rank: the max over ranks of each region
     regions = {k: max_over_ranks(v, dev, world) for k, v in regions.items()}
     name = min(regions, key=regions.get) if args.timing == "auto" else (
         "graph" if "graph" in regions and args.timing == "graph" else "eager")
-    return regions[name], name, kt, regions
+    return regions[name], name, kt, regions, outputs
+
+
+def last_outputs(wl):
+    """What the most recent step handed its caller, as host arrays: the loss, the model output and
+    every parameter after the step's Adam update. Float32 (float64 for a float64 tensor); an array
+    above its share of DUMP_BYTES is a fixed seeded sample of its elements (flattened, in index order)."""
+    torch.cuda.synchronize()
+    tensors = dict(wl.extra["last"])
+    params = [p for g in wl.extra["optimizer"].param_groups for p in g["params"]]
+    tensors.update({f"param_{i:03d}": p for i, p in enumerate(params)})
+    cap = max(1, (DUMP_BYTES // len(tensors) - 1024) // 8)  # elements per array: 8 bytes each + the file header
+    out = {}
+    for name, t in tensors.items():
+        t = t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dominant_class(wl):
@@ -687,16 +749,22 @@ def psnr_check(args, dev):
 
 # ------------------------------------------------------------------------------ per-config line
 def measure(cfg, args, dev, rank, world, with_kernels=True):
+    """One config's line. A plain run: build, warm up, time, dump. with_kernels (--full only) first
+    finds the dominant kernel class (steps of its own) and times its launches in the eager region."""
     from siren_mri_amd import _native
     wl = build(cfg, args, dev, rank, world)
-    for _ in range(2):
-        wl.step()
-    torch.cuda.synchronize()
-    totals = dominant_class(wl) if (with_kernels and wl.precision == "bf16") else {}
+    totals = {}
+    if args.full:
+        for _ in range(2):
+            wl.step()
+        torch.cuda.synchronize()
+        totals = dominant_class(wl) if (with_kernels and wl.precision == "bf16") else {}
     dom = max(totals, key=lambda k: totals[k][0]) if totals else None
     per_step = totals[dom][1] if dom else 0
-    elapsed, region, kt, regions = run_timed(wl, args, dev, world, kclass=dom,
-                                             max_launches=max(64, (per_step + 1) * args.steps))
+    elapsed, region, kt, regions, outputs = run_timed(wl, args, dev, world, kclass=dom,
+                                                      max_launches=max(64, (per_step + 1) * args.steps))
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     graph = region == "graph"
     ms = elapsed / args.steps * 1e3
     step_flops = wl.flops
@@ -708,7 +776,7 @@ def measure(cfg, args, dev, rank, world, with_kernels=True):
            "step_roofline": {"bound": "mfma", "flops_per_step_per_gpu": step_flops,
                              "achieved_tflops": round(step_flops / (ms * 1e-3) / 1e12, 2),
                              "peak_tflops": peak / 1e12, "frac": round(step_flops / (ms * 1e-3) / peak, 4)}}
-    if "encoder_flops_per_step" in wl.extra:
+    if "encoder_flops_per_step" in wl.extra and args.full:
         res["encoder"] = {"flops_per_step_per_gpu": wl.extra["encoder_flops_per_step"],
                           "precision": wl.extra["encoder_precision"],
                           "share_of_step_flops": round(wl.extra["encoder_flops_per_step"] /
@@ -828,7 +896,7 @@ def main():
         result["encoder"] = res["encoder"]
     # north_star's per-kernel target: bf16-MFMA utilisation of the fused SineLayer GEMM (the whole
     # forward: every layer's GEMM + bias + sine in one launch), from the same HIP-event timer
-    if wl.precision == "bf16" and 4 in totals:
+    if args.full and wl.precision == "bf16" and 4 in totals:
         if dom == 4 and "roofline" in res:
             f_ms, f_n = res["roofline"]["avg_launch_ms"], res["roofline"]["launches"]
         else:
@@ -843,10 +911,11 @@ def main():
             "mfma_peak_tflops": PEAK["bf16"] / 1e12, "mfma_frac": round(f_flops / (f_ms * 1e-3) / PEAK["bf16"], 4)}
     del wl
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_psnr and args.config == "m":
+    if args.full and rank == 0 and world == 1 and not args.no_psnr and args.config == "m":
         result["psnr"] = psnr_check(args, dev)
-    if world == 1 and not args.no_other_configs and args.config == "m":
+    if args.full and world == 1 and not args.no_other_configs and args.config == "m":
         oargs = argparse.Namespace(**vars(args))
+        oargs.dump_outputs = None
         others = {}
         for cfg in ("c1", "c2", "c3", "c4", "c4_fp32", "m_fp32", "m_shard8"):
             oargs.steps, oargs.warmup = CONFIG_DEFAULT_STEPS[cfg]
@@ -864,7 +933,7 @@ def main():
             # 1/8 shard (no all-reduce; SURVEY.md §8(d) target >= 6.5x)
             others["m_shard8"]["strong_scaling_bound_8gpu"] = round(res["ms_per_step"] / sh["ms_per_step"], 2)
         result["configs"] = others
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the metric config's CPU sample: 3 warm-up + 5 timed full steps need ~20 s
         result["cpu_baseline"] = cpu_baseline(args.config, max(args.cpu_budget_s, 24.0 if args.config == "m" else 0.0))
         if args.config == "m" and not args.no_other_configs:

@@ -11,7 +11,7 @@ for i in $(seq 1 "$N"); do
   if (( i % 2 == 0 )); then order=$(printf '%s\n' "${libs[@]}" | tac); else order=$(printf '%s\n' "${libs[@]}"); fi
   for lib in $order; do
     sleep 3
-    out=$(SIREN_MRI_AMD_LIB=$lib timeout -k 10 120 python -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-psnr --no-other-configs --timing eager 2>/dev/null)
+    out=$(SIREN_MRI_AMD_LIB=$lib timeout -k 10 120 python -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-psnr --no-other-configs --timing eager 2>/dev/null)
     python3 -c "import json,sys; d=json.loads(sys.argv[2]); print(sys.argv[1], round(d['ms_per_step'],4), d['roofline']['kernel_ms_per_step'])" "$(basename $lib)" "$out"
   done
 done
