@@ -25,6 +25,27 @@ def base_parser(batch_size=1, lr=1e-4, num_epochs=10000, epochs_til_ckpt=25, ste
     return p
 
 
+# --loss: the reference's MRI scripts pick one of these by commenting lines in and out
+# (train_mri_neural_process.py:169-171, train_mri_neural_process_ddp.py:241-244)
+LOSS_NAMES = {"mse": "image_hypernetwork_loss", "asinh": "image_hypernetwork_asinh_loss",
+              "perp": "image_hypernetwork_perp_loss", "l1": "image_hypernetwork_l1_loss",
+              "log": "image_hypernetwork_log_loss", "cubic": "image_hypernetwork_cubic_loss",
+              "ift": "image_hypernetwork_ift_loss"}
+
+
+def add_loss_argument(p):
+    p.add_argument("--loss", default="mse", choices=list(LOSS_NAMES),
+                   help="image loss of the hypernetwork objective (mse = image_mse, the default)")
+
+
+def hypernetwork_loss(name):
+    """The loss_functions.image_hypernetwork_*_loss function of a --loss name."""
+    from siren_mri_amd import loss_functions
+    if name not in LOSS_NAMES:
+        raise ValueError(f"unknown loss {name!r}; one of {', '.join(LOSS_NAMES)}")
+    return getattr(loss_functions, LOSS_NAMES[name])
+
+
 def psnr_summary(key="img"):
     """summary_fn(model, model_input, gt, model_output, writer, total_steps): logs PSNR."""
     from siren_mri_amd import utils

@@ -3,18 +3,19 @@
 CS-Cartesian masks. fastMRI is not available: seeded synthetic k-space phantoms (bug 0.7).
 The reference wraps the model in nn.DataParallel; here one process drives one GPU (use the
 _ddp script for several)."""
-from _common import base_parser, psnr_summary  # noqa: E402
+from _common import add_loss_argument, base_parser, hypernetwork_loss, psnr_summary  # noqa: E402
 
 from functools import partial
 
 import torch
 from torch.utils.data import DataLoader
 
-from siren_mri_amd import dataio, loss_functions, meta_modules, training
+from siren_mri_amd import dataio, meta_modules, training
 from siren_mri_amd.features import GaussianFourierFeatureTransform
 
 p = base_parser(batch_size=100, lr=6e-5, num_epochs=401, epochs_til_ckpt=10, steps_til_summary=100)
 p.add_argument("--train_sparsity_range", type=int, nargs="+", default=[2000, 4000])
+add_loss_argument(p)
 p.add_argument("--n_slices", type=int, default=1000, help="synthetic training slices")
 opt = p.parse_args()
 
@@ -51,6 +52,6 @@ fourier_transformer.save_B("current_B.pt")
 training.train(model=model, train_dataloader=dataloader, val_dataloader=dataloader_val, epochs=opt.num_epochs,
                lr=opt.lr, steps_til_summary=opt.steps_til_summary, epochs_til_checkpoint=opt.epochs_til_ckpt,
                model_dir=f"{opt.logging_root}/{opt.experiment_name}", overwrite=opt.overwrite,
-               loss_fn=partial(loss_functions.image_hypernetwork_loss, None, kl_weight, fw_weight),
+               loss_fn=partial(hypernetwork_loss(opt.loss), None, kl_weight, fw_weight),
                summary_fn=psnr_summary(), clip_grad=True, fourier_feat_transformer=fourier_transformer,
                device=device, accumulation_steps=4)

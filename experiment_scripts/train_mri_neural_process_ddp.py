@@ -15,7 +15,7 @@ the first step, so a crashed or preempted run still has the B its checkpoints we
 On resume (--checkpoint_path) B is read back — from --b_path, or from the checkpoint's run
 directory (<run>/checkpoints/model_*.pth -> <run>/current_B_DDP_mp<rank>.pt) — instead of drawing
 a new one: the hypernetwork weights only make sense with the B they were trained against."""
-from _common import base_parser, psnr_summary  # noqa: E402
+from _common import add_loss_argument, base_parser, hypernetwork_loss, psnr_summary  # noqa: E402
 
 import os
 from functools import partial
@@ -25,7 +25,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
-from siren_mri_amd import checkpoints, dataio, loss_functions, meta_modules, training_ddp
+from siren_mri_amd import checkpoints, dataio, meta_modules, training_ddp
 from siren_mri_amd.features import GaussianFourierFeatureTransform
 
 CONFIGS = {
@@ -42,6 +42,7 @@ CONFIGS = {
 
 p = base_parser(batch_size=32, lr=None, num_epochs=200, epochs_til_ckpt=5, steps_til_summary=100)
 p.add_argument("--config", default="hyperoptIV_homebrew", choices=sorted(CONFIGS))
+add_loss_argument(p)
 p.add_argument("--n_slices", type=int, default=1024)
 p.add_argument("--accumulation_steps", type=int, default=1)
 p.add_argument("--b_path", default=None, help="B matrix file to resume with (default: the checkpoint's run dir)")
@@ -103,7 +104,7 @@ model_dir = f"{opt.logging_root}/{opt.experiment_name}"
 training_ddp.train_ddp(model=model, train_dataloader=dataloader, epochs=opt.num_epochs, lr=lr,
                        steps_til_summary=opt.steps_til_summary, epochs_til_checkpoint=opt.epochs_til_ckpt,
                        model_dir=model_dir,
-                       loss_fn=partial(loss_functions.image_hypernetwork_loss, None, cfg["kl_weight"], cfg["fw_weight"]),
+                       loss_fn=partial(hypernetwork_loss(opt.loss), None, cfg["kl_weight"], cfg["fw_weight"]),
                        summary_fn=psnr_summary(), clip_grad=True, fourier_feat_transformer=fourier_transformer,
                        device=device, accumulation_steps=opt.accumulation_steps, ddp_run=True,
                        model_dir_hook=write_b_files)

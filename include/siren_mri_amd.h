@@ -442,6 +442,61 @@ int siren_kspace_sse_backward(const float* d, const float* mask, const float* hf
                               int channels, float noise, const float* g, float scale, float* dpred, void* stream);
 
 /*
+ * The k-space loss family of the MRI fork, on the same layout (pred, tgt, dpred [batch, npix,
+ * channels]; k0, mask [batch, channels, npix] or both NULL). With k0 and mask the loss is taken of
+ * y = DC(pred) (siren_dc_forward's arithmetic) and the backward carries the DC's coefficient; t = tgt.
+ *   SIREN_KLOSS_ASINH  weight sum (asinh(scale y) / divisor - asinh(scale t) / divisor)^2
+ *                      replaces image_asinh (loss_functions.py:119-141)
+ *   SIREN_KLOSS_CUBIC  weight sum (c(y) - c(t))^2, c(x) = sign(x) (|x| + eps)^(1/3)
+ *                      replaces image_mse_cubic (loss_functions.py:46-64)
+ *   SIREN_KLOSS_SMAPE  weight sum |y - t| / (eps + |t| + |y|)
+ *                      replaces image_smape (loss_functions.py:103-117)
+ *   SIREN_KLOSS_L1     weight sum |y - t|
+ *                      replaces kspace_l1 (loss_functions.py:169-190; its sparsity term has weight 0)
+ *   SIREN_KLOSS_PERP   weight sum_pixels |y_re t_im - y_im t_re| / (|y| + eps), channels == 2
+ *                      replaces image_perp (loss_functions.py:143-167)
+ *   SIREN_KLOSS_LOG    weight sum_pixels mag_weight (log(|y| + eps) - log(|t| + eps))^2
+ *                      + phase_weight (2 - cos(arg y - arg t)), channels == 2
+ *                      replaces image_mse_log (loss_functions.py:12-44)
+ * The sums run over every element (the batch included); |.| and arg are those of the complex number
+ * (channel 0, channel 1). At zero the gradients are torch autograd's, which the reference runs on:
+ * sign(0) = 0, d|x|/dx = 0 at 0, the gradients of a complex magnitude and angle are 0 at 0, arg 0 = 0;
+ * an element with y == t has a gradient of exactly 0. The constants travel in siren_kloss_desc
+ * (fields a kind does not use are ignored).
+ * siren_kspace_loss_forward   *loss = the scalar (device), one launch, deterministic summation order;
+ *                    workspace as siren_sse_forward's (siren_sse_workspace_bytes()). Nothing is kept
+ *                    for the backward.
+ * siren_kspace_loss_backward  dpred = g[0] dL/dy coef(mask) (coef = 1 without DC), recomputed from pred,
+ *                    tgt (and the planes) in one launch: the loss's and the data consistency's autograd
+ *                    backward in one pass.
+ */
+enum {
+  SIREN_KLOSS_ASINH = 0,
+  SIREN_KLOSS_CUBIC = 1,
+  SIREN_KLOSS_SMAPE = 2,
+  SIREN_KLOSS_L1 = 3,
+  SIREN_KLOSS_PERP = 4,
+  SIREN_KLOSS_LOG = 5,
+  SIREN_KLOSS_KINDS = 6
+};
+
+typedef struct siren_kloss_desc {
+  float weight;       /* of the whole sum                                      */
+  float eps;          /* cubic, smape, log: 1e-3; perp: 1e-8 in the reference  */
+  float scale;        /* asinh: 400                                            */
+  float divisor;      /* asinh: 6.7                                            */
+  float mag_weight;   /* log: 1e-4                                             */
+  float phase_weight; /* log: 1e-4                                             */
+} siren_kloss_desc;
+
+int siren_kspace_loss_forward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                              const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                              float noise, float* loss, void* workspace, int64_t ws_bytes, void* stream);
+int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                               const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                               float noise, const float* g, float* dpred, void* stream);
+
+/*
  * Gaussian Fourier features (replaces GaussianFourierFeatureTransform.forward, features.py:31-41):
  * out [rows, 2 m] = cat(sin(2 pi x B), cos(2 pi x B)) for x [rows, cin], B [cin, m] (device float32),
  * one launch. Feeds the SIREN's wide first layer (5..16 inputs on the register-resident forward).

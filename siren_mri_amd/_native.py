@@ -84,6 +84,8 @@ EXPORTED_SYMBOLS = (
     "siren_dc_backward",
     "siren_kspace_sse_forward",
     "siren_kspace_sse_backward",
+    "siren_kspace_loss_forward",
+    "siren_kspace_loss_backward",
     "siren_fourier_features",
     "siren_sincos_f32",
     "siren_last_error",
@@ -141,6 +143,29 @@ class SirenLossDesc(ctypes.Structure):
         ("loss", ctypes.c_void_p),
         ("loss_workspace", ctypes.c_void_p),
         ("loss_workspace_bytes", ctypes.c_int64),
+    ]
+
+
+# siren_kspace_loss_forward / _backward kinds (SIREN_KLOSS_* of include/siren_mri_amd.h)
+KLOSS_ASINH = 0
+KLOSS_CUBIC = 1
+KLOSS_SMAPE = 2
+KLOSS_L1 = 3
+KLOSS_PERP = 4
+KLOSS_LOG = 5
+KLOSS_KINDS = 6
+
+
+class SirenKlossDesc(ctypes.Structure):
+    """Mirror of ``siren_kloss_desc`` (include/siren_mri_amd.h)."""
+
+    _fields_ = [
+        ("weight", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("scale", ctypes.c_float),
+        ("divisor", ctypes.c_float),
+        ("mag_weight", ctypes.c_float),
+        ("phase_weight", ctypes.c_float),
     ]
 
 
@@ -333,6 +358,11 @@ def _declare(lib):
     lib.siren_kspace_sse_forward.restype = ci
     lib.siren_kspace_sse_backward.argtypes = [vp, vp, vp, i64, i64, ci, f32, vp, f32, vp, vp]
     lib.siren_kspace_sse_backward.restype = ci
+    KP = ctypes.POINTER(SirenKlossDesc)
+    lib.siren_kspace_loss_forward.argtypes = [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, i64, vp]
+    lib.siren_kspace_loss_forward.restype = ci
+    lib.siren_kspace_loss_backward.argtypes = [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, vp]
+    lib.siren_kspace_loss_backward.restype = ci
     lib.siren_fourier_features.argtypes = [vp, vp, i64, ci, ci, vp, vp]
     lib.siren_fourier_features.restype = ci
     lib.siren_sincos_f32.argtypes = [vp, vp, vp, i64, ci, vp]

@@ -17,6 +17,7 @@
 #include "siren_adam.hip"
 #include "siren_loss.hip"
 #include "siren_kspace.hip"
+#include "siren_kloss.hip"
 #include "siren_encoder.hip"
 #include "siren_conv.hip"
 #include "siren_f64.hip"
@@ -3062,6 +3063,94 @@ int siren_kspace_sse_backward(const float* d, const float* mask, const float* hf
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KS_THREADS)));
   hipLaunchKernelGGL(ksse_bwd_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("kspace_sse_backward");
+}
+
+namespace {
+// one launch of KERNEL<kind> (kind checked by kloss_check)
+#define KLOSS_LAUNCH(KERNEL, kind, blocks, stream, a)                                                   \
+  do {                                                                                                   \
+    switch (kind) {                                                                                      \
+      case SIREN_KLOSS_ASINH: hipLaunchKernelGGL(KERNEL<KL_ASINH>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_CUBIC: hipLaunchKernelGGL(KERNEL<KL_CUBIC>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_SMAPE: hipLaunchKernelGGL(KERNEL<KL_SMAPE>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_L1: hipLaunchKernelGGL(KERNEL<KL_L1>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;       \
+      case SIREN_KLOSS_PERP: hipLaunchKernelGGL(KERNEL<KL_PERP>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;   \
+      default: hipLaunchKernelGGL(KERNEL<KL_LOG>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;                  \
+    }                                                                                                    \
+  } while (0)
+
+// the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
+int kloss_check(const char* what, int kind, const siren_kloss_desc* desc, const float* k0, const float* mask,
+                int64_t batch, int64_t npix, int channels) {
+  if (kind < 0 || kind >= SIREN_KLOSS_KINDS)
+    return fail(SIREN_EINVAL, "%s: kind %d outside [0, %d)", what, kind, (int)SIREN_KLOSS_KINDS);
+  if (!desc) return fail(SIREN_EINVAL, "%s: null descriptor", what);
+  if (channels < 1 || channels > KL_MAXC)
+    return fail(SIREN_EINVAL, "%s: channels %d outside [1, %d]", what, channels, KL_MAXC);
+  if ((kind == SIREN_KLOSS_PERP || kind == SIREN_KLOSS_LOG) && channels != 2)
+    return fail(SIREN_EINVAL, "%s: kind %d (%s) takes complex pixels, channels == 2, got %d", what, kind,
+                kind == SIREN_KLOSS_PERP ? "perp" : "log", channels);
+  if ((!k0) != (!mask)) return fail(SIREN_EINVAL, "%s: k0 and mask go together (data consistency)", what);
+  if (batch < 0 || npix < 0)
+    return fail(SIREN_EINVAL, "%s: bad sizes (batch=%lld, npix=%lld)", what, (long long)batch, (long long)npix);
+  return SIREN_OK;
+}
+
+KlossArgs kloss_args(const siren_kloss_desc* d, const float* pred, const float* k0, const float* mask,
+                     const float* tgt, int64_t batch, int64_t npix, int channels, float noise) {
+  KlossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.k0 = k0;
+  a.mask = mask;
+  a.tgt = tgt;
+  a.batch = batch;
+  a.npix = npix;
+  a.C = channels;
+  a.noise = noise;
+  a.weight = d->weight;
+  a.eps = d->eps;
+  a.scale = d->scale;
+  a.divisor = d->divisor;
+  a.mag_weight = d->mag_weight;
+  a.phase_weight = d->phase_weight;
+  return a;
+}
+}  // namespace
+
+int siren_kspace_loss_forward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                              const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                              float noise, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = kloss_check("kspace_loss_forward", kind, desc, k0, mask, batch, npix, channels)) return rc;
+  if (!loss || (batch * npix > 0 && (!pred || !tgt))) return fail(SIREN_EINVAL, "kspace_loss_forward: null pointer");
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "kspace_loss_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  static_assert(KL_MAX_BLOCKS == SSE_MAX_BLOCKS, "the hand-off's slots are siren_sse_workspace_bytes()'s");
+  KlossArgs a = kloss_args(desc, pred, k0, mask, tgt, batch, npix, channels, noise);
+  a.out = loss;
+  a.partial = (float*)workspace;
+  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
+  // 8 coordinates per thread, as kspace_sse_forward: few blocks for the hand-off counter
+  const unsigned blocks =
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(KL_MAX_BLOCKS, cdiv(batch * npix, 8 * KL_THREADS)));
+  KLOSS_LAUNCH(kloss_fwd_kernel, kind, blocks, (hipStream_t)stream, a);
+  return check_launch("kspace_loss_forward");
+}
+
+int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                               const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                               float noise, const float* g, float* dpred, void* stream) {
+  if (int rc = kloss_check("kspace_loss_backward", kind, desc, k0, mask, batch, npix, channels)) return rc;
+  if (batch * npix > 0 && (!pred || !tgt || !g || !dpred))
+    return fail(SIREN_EINVAL, "kspace_loss_backward: null pointer");
+  if (batch * npix == 0) return SIREN_OK;
+  KlossArgs a = kloss_args(desc, pred, k0, mask, tgt, batch, npix, channels, noise);
+  a.g = g;
+  a.out = dpred;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KL_THREADS)));
+  KLOSS_LAUNCH(kloss_bwd_kernel, kind, blocks, (hipStream_t)stream, a);
+  return check_launch("kspace_loss_backward");
 }
 
 int siren_fourier_features(const float* x, const float* B, int64_t rows, int cin, int m, float* out, void* stream) {

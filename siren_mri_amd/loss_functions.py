@@ -4,16 +4,25 @@
   latent_loss              loss_functions.py:275-276
   hypo_weight_loss         loss_functions.py:279-287
   image_hypernetwork_loss  loss_functions.py:290-293
+  image_mse_log, image_mse_cubic, image_smape, image_asinh, image_perp, kspace_l1
+                           loss_functions.py:12-64, 103-190 (the k-space loss family)
+  ift_image_mse, image_l1  loss_functions.py:192-235
+  image_hypernetwork_{perp,asinh,l1,log,cubic,ift}_loss  loss_functions.py:295-323
   function_mse             loss_functions.py:326-327
   gradients_mse            loss_functions.py:330-335
   laplace_mse              loss_functions.py:350-355
 
 image_mse runs on the native k-space op (siren_kspace.hip), with the data consistency of a native
-DataConsistencyInKspace output folded in.
+DataConsistencyInKspace output folded in. The six k-space losses of the
+family run on siren_mri_amd::kspace_loss (siren_kloss.hip: one forward and one backward launch, the
+DC folded in the same way); ift_image_mse and image_l1 are PyTorch compositions.
 
 Deliberate deviation (bug 0.2): the reference builds its high-frequency mask
 on a fixed 128x128 grid, so image_mse(high_freq=True) raises for any other image size; here the
 mask applies when the image is 128x128 and the loss is the plain SSE otherwise.
+
+Deliberate deviation: image_mse_log does not print its two partial sums on every call
+(loss_functions.py:37); that print forces a host synchronisation per step.
 """
 from __future__ import annotations
 
@@ -319,6 +328,278 @@ def hypo_weight_loss(model_output):
 
 def image_hypernetwork_loss(mask, kl, fw, model_output, gt):
     return {"img_loss": image_mse(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+# The k-space loss family on the SIREN output layout [B, N, C], optionally with data consistency
+# folded in (siren_kloss.hip):
+#   siren_mri_amd::kspace_loss(pred, k0?, mask?, tgt, kind, noise) -> loss
+#   siren_mri_amd::kspace_loss_bwd(pred, k0?, mask?, tgt, g, kind, noise) -> dpred
+# The backward recomputes dL/dy from its inputs: the forward saves no residual tensor.
+_LIB.define("kspace_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, int kind, float noise) -> Tensor")
+_LIB.define("kspace_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor g, int kind, float noise) "
+            "-> Tensor")
+
+
+def _kloss_desc(weight=1.0, eps=0.0, scale=0.0, divisor=1.0, mag_weight=0.0, phase_weight=0.0):
+    return _native.SirenKlossDesc(weight, eps, scale, divisor, mag_weight, phase_weight)
+
+
+# the reference's constants, per kind (loss_functions.py:25-35, 52-57, 110-111, 127-135, 156-161, 183)
+_KLOSS_DESCS = {
+    _native.KLOSS_ASINH: _kloss_desc(weight=1 / (128 * 128), scale=400.0, divisor=6.7),
+    _native.KLOSS_CUBIC: _kloss_desc(weight=0.000001, eps=1e-3),
+    _native.KLOSS_SMAPE: _kloss_desc(weight=1 / (128 * 128), eps=1e-3),
+    _native.KLOSS_L1: _kloss_desc(weight=1 / (128 * 128)),
+    _native.KLOSS_PERP: _kloss_desc(weight=1 / (128 * 128) * 1000, eps=1e-8),
+    _native.KLOSS_LOG: _kloss_desc(weight=1.0, eps=1e-3, mag_weight=0.0001, phase_weight=0.0001),
+}
+
+
+def _kloss_desc_ref(kind):
+    import ctypes
+    desc = _KLOSS_DESCS.get(int(kind))
+    # an unknown kind goes to the library with some descriptor: its argument check reports it
+    return ctypes.byref(desc if desc is not None else _KLOSS_DESCS[_native.KLOSS_L1])
+
+
+def _kloss_operands(pred, k0, mask, tgt):
+    """Contiguous fp32 operands of the two ops, shapes checked (the kernels index by pred's shape)."""
+    if pred.dim() != 3 or tgt.shape != pred.shape:
+        raise RuntimeError(f"siren_mri_amd.kspace_loss: pred {tuple(pred.shape)} must be [B, N, C] and tgt "
+                           f"{tuple(tgt.shape)} of the same shape")
+    b, n, c = pred.shape
+    for name, t in (("k0", k0), ("mask", mask)):
+        if t is not None and (t.dim() < 3 or t.shape[0] != b or t.shape[1] != c or t.numel() != pred.numel()):
+            raise RuntimeError(f"siren_mri_amd.kspace_loss: {name} planes {tuple(t.shape)} do not match the "
+                               f"prediction {tuple(pred.shape)}")
+    for name, t in (("pred", pred), ("k0", k0), ("mask", mask), ("tgt", tgt)):
+        if t is not None and (t.dtype != torch.float32 or t.device != pred.device):
+            raise RuntimeError(f"siren_mri_amd.kspace_loss: {name} must be float32 on {pred.device}")
+    return (b, n, c, pred.contiguous(), k0.contiguous() if k0 is not None else None,
+            mask.contiguous() if mask is not None else None, tgt.contiguous())
+
+
+def _kspace_loss_cuda(pred, k0, mask, tgt, kind, noise):
+    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    ws = _sse_workspace(pred.device)
+    rc = _native.lib().siren_kspace_loss_forward(
+        int(kind), _kloss_desc_ref(kind), pc.data_ptr(), kc.data_ptr() if kc is not None else None,
+        mc.data_ptr() if mc is not None else None, tc.data_ptr(), b, n, c, float(noise), loss.data_ptr(),
+        ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
+    _native.check(rc, "siren_kspace_loss_forward")
+    return loss
+
+
+def _kspace_loss_bwd_cuda(pred, k0, mask, tgt, g, kind, noise):
+    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
+    if g.numel() != 1 or g.device != pred.device:
+        raise RuntimeError("siren_mri_amd.kspace_loss_bwd: g must be one element on the prediction's device")
+    gc = g.contiguous().to(torch.float32)
+    out = torch.empty_like(pc)
+    rc = _native.lib().siren_kspace_loss_backward(
+        int(kind), _kloss_desc_ref(kind), pc.data_ptr(), kc.data_ptr() if kc is not None else None,
+        mc.data_ptr() if mc is not None else None, tc.data_ptr(), b, n, c, float(noise), gc.data_ptr(),
+        out.data_ptr(), _native.stream_handle(pred.device))
+    _native.check(rc, "siren_kspace_loss_backward")
+    return out
+
+
+class _KspaceLossAutograd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, k0, mask, tgt, kind, noise):
+        with torch._C._AutoDispatchBelowAutograd():
+            loss = torch.ops.siren_mri_amd.kspace_loss(pred, k0, mask, tgt, kind, noise)
+        ctx.save_for_backward(pred, k0, mask, tgt)  # the op's own inputs: no residual is kept
+        ctx.kind, ctx.noise = kind, noise
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 6
+        if torch.is_grad_enabled():
+            raise RuntimeError("siren_mri_amd: double backward through the native k-space loss is not provided; "
+                               "run it on the expression path (siren_mri_amd.loss_functions."
+                               "set_kspace_loss_native(False))")
+        pred, k0, mask, tgt = ctx.saved_tensors
+        dpred = torch.ops.siren_mri_amd.kspace_loss_bwd(pred, k0, mask, tgt, g, ctx.kind, ctx.noise)
+        return dpred, None, None, None, None, None
+
+
+_LIB.impl("kspace_loss", _kspace_loss_cuda, "CUDA")
+_LIB.impl("kspace_loss_bwd", _kspace_loss_bwd_cuda, "CUDA")
+_LIB.impl("kspace_loss", lambda pred, k0, mask, tgt, kind, noise:
+          _KspaceLossAutograd.apply(pred, k0, mask, tgt, kind, noise), "Autograd")
+torch.library.register_fake("siren_mri_amd::kspace_loss", lambda pred, k0, mask, tgt, kind, noise: pred.new_empty(()),
+                            lib=_LIB)
+torch.library.register_fake("siren_mri_amd::kspace_loss_bwd",
+                            lambda pred, k0, mask, tgt, g, kind, noise: torch.empty_like(pred), lib=_LIB)
+
+_KLOSS_NATIVE = True
+
+
+def set_kspace_loss_native(enabled: bool) -> None:
+    """Run the k-space loss family on the native op where it applies (default on); off: the
+    reference's expression in PyTorch everywhere (A/B tests)."""
+    global _KLOSS_NATIVE
+    _KLOSS_NATIVE = bool(enabled)
+
+
+def _kspace_loss_native(out, tgt, kind):
+    """A loss of the family on [B, N, C] through the native op, or None when it does not apply."""
+    if not (_KLOSS_NATIVE and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3
+            and tgt.shape == out.shape and tgt.dtype == torch.float32 and tgt.device == out.device
+            and not tgt.requires_grad and 1 <= out.shape[-1] <= 8):
+        return None
+    if kind in (_native.KLOSS_PERP, _native.KLOSS_LOG) and out.shape[-1] != 2:
+        return None
+    src = dc_source(out) if _FUSE_DC else None
+    if src is not None and src[0].shape == out.shape:
+        pred, k0, mask, noise = src
+        return torch.ops.siren_mri_amd.kspace_loss(pred, k0, mask, tgt, kind, noise)
+    return torch.ops.siren_mri_amd.kspace_loss(out, None, None, tgt, kind, 0.0)
+
+
+def _complex_planes(t):
+    """[B, N, 2] -> the complex [B, H, W] image of its two channels (loss_functions.py:15-16)."""
+    real = lin2img(t)
+    return real, real[:, 0, :, :] + 1j * real[:, 1, :, :]
+
+
+def image_mse_log(mask, model_output, gt):
+    """loss_functions.py:12-44: squared difference of log magnitudes plus 2 - cos of the phase
+    difference, summed over the pixels (without the reference's per-call print of the two sums)."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_LOG)
+    if fused is not None:
+        return {"img_loss": fused}
+    _, kspace_output = _complex_planes(model_output["model_out"])
+    _, kspace_gt = _complex_planes(gt["img"])
+    eps = 1e-3
+    pred_log = torch.log(torch.abs(kspace_output) + eps)
+    gt_log = torch.log(torch.abs(kspace_gt) + eps)
+    mag_weight = 0.0001
+    phase_weight = 0.0001
+    loss = (mag_weight * (pred_log - gt_log) ** 2
+            + phase_weight * (2 - torch.cos(torch.angle(kspace_output) - torch.angle(kspace_gt)))).sum()
+    return {"img_loss": loss}
+
+
+def image_mse_cubic(mask, model_output, gt):
+    """loss_functions.py:46-64: SSE of the signed cube roots sign(x) (|x| + 1e-3)^(1/3), times 1e-6."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_CUBIC)
+    if fused is not None:
+        return {"img_loss": fused}
+    pred, tgt = lin2img(model_output["model_out"]), lin2img(gt["img"])
+    eps = 1e-3
+    pred_tx = torch.sign(pred) * torch.pow(torch.abs(pred) + eps, 1 / 3)
+    gt_tx = torch.sign(tgt) * torch.pow(torch.abs(tgt) + eps, 1 / 3)
+    return {"img_loss": 0.000001 * ((pred_tx - gt_tx) ** 2).sum()}
+
+
+def image_smape(mask, model_output, gt):
+    """loss_functions.py:103-117: sum |p - t| / (1e-3 + |t| + |p|) / 128^2."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_SMAPE)
+    if fused is not None:
+        return {"img_loss": fused}
+    pred, tgt = lin2img(model_output["model_out"]), lin2img(gt["img"])
+    eps = 1e-3
+    return {"img_loss": _KSPACE_WEIGHT * (torch.abs(pred - tgt) / (eps + torch.abs(tgt) + torch.abs(pred))).sum()}
+
+
+def image_asinh(mask, model_output, gt):
+    """loss_functions.py:119-141: SSE of asinh(400 x) / 6.7, over 128^2."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_ASINH)
+    if fused is not None:
+        return {"img_loss": fused}
+    pred = torch.asinh(400 * lin2img(model_output["model_out"])) / 6.7
+    tgt = torch.asinh(400 * lin2img(gt["img"])) / 6.7
+    return {"img_loss": _KSPACE_WEIGHT * ((pred - tgt) ** 2).sum()}
+
+
+def image_perp(mask, model_output, gt):
+    """loss_functions.py:143-167: the component of the target perpendicular to the prediction,
+    |Im(conj(p) t)| / (|p| + 1e-8), summed over the pixels, times 1000 / 128^2."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_PERP)
+    if fused is not None:
+        return {"img_loss": fused}
+    _, kspace_pred = _complex_planes(model_output["model_out"])
+    _, kspace_gt = _complex_planes(gt["img"])
+    eps = 1e-8
+    loss = torch.abs(torch.real(kspace_pred) * torch.imag(kspace_gt)
+                     - torch.imag(kspace_pred) * torch.real(kspace_gt)) / (torch.abs(kspace_pred) + eps)
+    return {"img_loss": 1 / (128 * 128) * 1000 * loss.sum()}
+
+
+def kspace_l1(mask, model_output, gt):
+    """loss_functions.py:169-190: sum |p - t| / 128^2 (the reference's sparsity term has weight 0)."""
+    fused = _kspace_loss_native(model_output["model_out"], gt["img"], _native.KLOSS_L1)
+    if fused is not None:
+        return {"img_loss": fused}
+    pred, tgt = lin2img(model_output["model_out"]), lin2img(gt["img"])
+    return {"img_loss": _KSPACE_WEIGHT * torch.abs(pred - tgt).sum()}
+
+
+def ift_image_mse(mask, model_output, gt):
+    """loss_functions.py:192-229: SSE of the magnitude images (ifft2 of the complex k-space, with the
+    optional mask), plus 1e-8 of the k-space magnitude sum, plus 0.0025 of the k-space SSE (the
+    native weighted SSE on the GPU)."""
+    out, tgt = model_output["model_out"], gt["img"]
+    _, kspace_output = _complex_planes(out)
+    _, kspace_gt = _complex_planes(tgt)
+    img_output = torch.abs(torch.fft.ifft2(kspace_output))
+    img_gt = torch.abs(torch.fft.ifft2(kspace_gt))
+    l1_cost = 1e-8 * torch.abs(kspace_output).sum()
+    kspace_loss = weighted_sse(out, tgt, weight=0.0025)
+    img = (img_output - img_gt) ** 2
+    if mask is not None:
+        img = mask * img
+    return {"img_loss": img.sum() + l1_cost + kspace_loss}
+
+
+def image_l1(mask, model_output, gt):
+    """loss_functions.py:231-235: mean |p - t|, with the optional mask."""
+    diff = torch.abs(model_output["model_out"] - gt["img"])
+    if mask is not None:
+        diff = mask * diff
+    return {"img_loss": diff.mean()}
+
+
+def image_hypernetwork_perp_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": image_perp(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+def image_hypernetwork_asinh_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": image_asinh(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+def image_hypernetwork_l1_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": kspace_l1(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+def image_hypernetwork_log_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": image_mse_log(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+def image_hypernetwork_cubic_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": image_mse_cubic(mask, model_output, gt)["img_loss"],
+            "latent_loss": kl * latent_loss(model_output),
+            "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
+
+
+def image_hypernetwork_ift_loss(mask, kl, fw, model_output, gt):
+    return {"img_loss": ift_image_mse(mask, model_output, gt)["img_loss"],
             "latent_loss": kl * latent_loss(model_output),
             "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
 
