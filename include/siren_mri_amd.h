@@ -513,7 +513,8 @@ int siren_sincos_f32(const float* x, float* s, float* c, int64_t n, int impl, vo
 
 /*
  * Process-wide execution options (no reference counterpart; used by tests and benchmarks to
- * compare code paths). Keys:
+ * compare code paths). The one list of keys, each with its range and default, is the table
+ * kOptions in siren_mri_amd/csrc/rt_common.hip; what the main keys select:
  *   "fused_forward"  1 (default): bf16 stacks of equal power-of-two hidden widths run their
  *                    forward as one kernel; 0: one kernel per layer.
  *   "fused_backward" 1 (default): bf16 backward folds the first layer's weight gradient into
@@ -567,10 +568,11 @@ int siren_sincos_f32(const float* x, float* s, float* c, int64_t n, int impl, vo
  *                    (all bit-identical).
  *   "debug_fused_profile"  device address of an int64 buffer [grid][4] that receives per-
  *                    workgroup cycle counts of the fused forward's phases, or 0 (off).
- * Returns SIREN_OK, or SIREN_EINVAL for an unknown key / value. Not thread-safe.
+ * Returns SIREN_OK, or SIREN_EINVAL for an unknown key or a value outside the key's range (the
+ * value then stays as it was). Not thread-safe.
  */
 int siren_config_set(const char* key, int64_t value);
-int64_t siren_config_get(const char* key); /* -1 for an unknown key */
+int64_t siren_config_get(const char* key); /* -1 for an unknown key and for the debug_*_profile addresses */
 
 /* Thread-local message of the last failing call ("" if none). */
 const char* siren_last_error(void);

@@ -24,74 +24,6 @@ LIB_NAME = "libsiren_mri_amd.so"
 # SIREN_MRI_AMD_LIB: load another build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("SIREN_MRI_AMD_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
-# Every symbol include/siren_mri_amd.h declares (checked by tests/test_native_abi.py).
-EXPORTED_SYMBOLS = (
-    "siren_mlp_check",
-    "siren_mlp_saved_bytes",
-    "siren_mlp_workspace_bytes",
-    "siren_mlp_forward",
-    "siren_mlp_backward",
-    "siren_mlp_loss_check",
-    "siren_mlp_forward_loss",
-    "siren_mlp_backward_ex",
-    "siren_mlp64_saved_bytes",
-    "siren_mlp64_workspace_bytes",
-    "siren_mlp64_forward",
-    "siren_mlp64_backward",
-    "siren_hyper_saved_bytes",
-    "siren_hyper_workspace_bytes",
-    "siren_hyper_forward",
-    "siren_hyper_backward",
-    "siren_jvp_saved_bytes",
-    "siren_jvp_workspace_bytes",
-    "siren_jvp_forward",
-    "siren_jvp_backward",
-    "siren_jvp_forward_ex",
-    "siren_jvp_backward_ex",
-    "siren_timing_enable",
-    "siren_timing_collect",
-    "siren_timing_disable",
-    "siren_config_set",
-    "siren_config_get",
-    "siren_adam_step",
-    "siren_adam_num_blocks",
-    "siren_adam_scalars",
-    "siren_adam_scalars_table",
-    "siren_sse_workspace_bytes",
-    "siren_enc_workspace_bytes",
-    "siren_conv_wrw_workspace_bytes",
-    "siren_conv_wrw_k5",
-    "siren_conv_fwd_k5",
-    "siren_conv_dgrad_k5_fused",
-    "siren_conv_fwd_k5_res",
-    "siren_conv_check",
-    "siren_conv_fwd",
-    "siren_conv_wrw_ws_bytes",
-    "siren_conv_wrw",
-    "siren_enc_bias_relu",
-    "siren_enc_prep",
-    "siren_sumsq_workspace_bytes",
-    "siren_sumsq_forward",
-    "siren_sumsq_backward",
-    "siren_enc_relu_bwd",
-    "siren_enc_res_fwd",
-    "siren_enc_res_bwd",
-    "siren_enc_pixfc_fwd",
-    "siren_enc_pixfc_bwd",
-    "siren_sse_forward",
-    "siren_sse_backward",
-    "siren_dc_forward",
-    "siren_dc_backward",
-    "siren_kspace_sse_forward",
-    "siren_kspace_sse_backward",
-    "siren_kspace_loss_forward",
-    "siren_kspace_loss_backward",
-    "siren_fourier_features",
-    "siren_sincos_f32",
-    "siren_last_error",
-    "siren_version",
-)
-
 KCLASS_FWD_GEMM = 1
 KCLASS_DX_GEMM = 2
 KCLASS_DW_GEMM = 3
@@ -227,150 +159,93 @@ _lib = None
 _lock = threading.Lock()
 
 
+def _signatures():
+    """symbol -> (restype, argtypes) of every function include/siren_mri_amd.h declares."""
+    ci, i64, f32, f64, vp, cstr = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
+                                   ctypes.c_char_p)
+    pvp, pi64 = ctypes.POINTER(vp), ctypes.POINTER(i64)
+    P, LP, HP = ctypes.POINTER(SirenMLPDesc), ctypes.POINTER(SirenLossDesc), ctypes.POINTER(SirenHyperDesc)
+    KP, AP = ctypes.POINTER(SirenKlossDesc), ctypes.POINTER(SirenAdamDesc)
+    fwd = [P, vp, vp, vp, i64, vp, i64, vp]                   # desc, x, y, saved, bytes, workspace, bytes, stream
+    bwd = [P, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]     # desc, x, dy, saved, .., dweight, dbias, dx, stream
+    return {
+        "siren_mlp_check": (ci, [P]),
+        "siren_mlp_saved_bytes": (i64, [P]),
+        "siren_mlp_workspace_bytes": (i64, [P]),
+        "siren_mlp_forward": (ci, fwd),
+        "siren_mlp_backward": (ci, bwd),
+        "siren_mlp_loss_check": (ci, [P, LP]),
+        "siren_mlp_forward_loss": (ci, [P, LP, vp, vp, vp, i64, vp, i64, vp]),
+        "siren_mlp_backward_ex": (ci, [P, vp, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]),
+        "siren_mlp64_saved_bytes": (i64, [P]),
+        "siren_mlp64_workspace_bytes": (i64, [P]),
+        "siren_mlp64_forward": (ci, fwd),
+        "siren_mlp64_backward": (ci, bwd),
+        "siren_hyper_saved_bytes": (i64, [HP]),
+        "siren_hyper_workspace_bytes": (i64, [HP]),
+        "siren_hyper_forward": (ci, [HP, vp, pvp, vp, i64, vp]),
+        "siren_hyper_backward": (ci, [HP, vp, pvp, vp, i64, vp, i64, pvp, pvp, vp, vp]),
+        "siren_jvp_saved_bytes": (i64, [P, ci]),
+        "siren_jvp_workspace_bytes": (i64, [P, ci]),
+        "siren_jvp_forward": (ci, [P, ci, vp, vp, vp, vp, i64, vp, i64, vp]),
+        "siren_jvp_backward": (ci, [P, ci, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]),
+        "siren_jvp_forward_ex": (ci, [P, ci, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]),
+        "siren_jvp_backward_ex": (ci, [P, ci, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp, i64, vp]),
+        "siren_timing_enable": (ci, [ci, ci]),
+        "siren_timing_collect": (ci, [ctypes.POINTER(f64), pi64]),
+        "siren_timing_disable": (None, []),
+        "siren_config_set": (ci, [cstr, i64]),
+        "siren_config_get": (i64, [cstr]),
+        "siren_adam_step": (ci, [AP, vp]),
+        "siren_adam_num_blocks": (i64, [AP]),
+        "siren_adam_scalars": (ci, [vp, f64, f64, f64, vp, vp]),
+        "siren_adam_scalars_table": (ci, [vp, vp, i64, vp, vp]),
+        "siren_sse_workspace_bytes": (i64, []),
+        "siren_enc_workspace_bytes": (i64, []),
+        "siren_conv_wrw_workspace_bytes": (i64, [ci, ci, ci]),
+        "siren_conv_wrw_k5": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, i64, vp]),
+        "siren_conv_fwd_k5": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]),
+        "siren_conv_dgrad_k5_fused": (ci, [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, i64, vp]),
+        "siren_conv_fwd_k5_res": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "siren_conv_check": (ci, [ci, ci, ci, ci, ci, ci, ci]),
+        "siren_conv_fwd": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]),
+        "siren_conv_wrw_ws_bytes": (i64, [ci, ci, ci, ci, ci, ci]),
+        "siren_conv_wrw": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, i64, vp]),
+        "siren_enc_bias_relu": (ci, [vp, vp, i64, ci, vp]),
+        "siren_enc_prep": (ci, [ci, pvp, pvp, pi64, pvp, pvp, pvp, vp]),
+        "siren_sumsq_workspace_bytes": (i64, [i64]),
+        "siren_sumsq_forward": (ci, [ci, pvp, pi64, vp, vp, i64, vp]),
+        "siren_sumsq_backward": (ci, [ci, pvp, pi64, vp, pvp, vp]),
+        "siren_enc_relu_bwd": (ci, [vp, vp, vp, vp, vp, i64, ci, vp, i64, vp]),
+        "siren_enc_res_fwd": (ci, [vp, vp, vp, vp, i64, ci, vp]),
+        "siren_enc_res_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, vp, i64, vp]),
+        "siren_enc_pixfc_fwd": (ci, [vp, vp, vp, vp, vp, ci, i64, ci, vp, i64, vp]),
+        "siren_enc_pixfc_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, i64, ci, vp, i64, vp]),
+        "siren_sse_forward": (ci, [vp, vp, vp, i64, i64, f32, vp, vp, vp, i64, vp]),
+        "siren_sse_backward": (ci, [vp, vp, i64, i64, vp, f32, vp, vp]),
+        "siren_dc_forward": (ci, [vp, vp, vp, i64, i64, ci, f32, vp, vp]),
+        "siren_dc_backward": (ci, [vp, vp, i64, i64, ci, f32, vp, vp]),
+        "siren_kspace_sse_forward": (ci, [vp, vp, vp, vp, vp, i64, i64, ci, f32, f32, vp, vp, vp, i64, vp]),
+        "siren_kspace_sse_backward": (ci, [vp, vp, vp, i64, i64, ci, f32, vp, f32, vp, vp]),
+        "siren_kspace_loss_forward": (ci, [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, i64, vp]),
+        "siren_kspace_loss_backward": (ci, [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, vp]),
+        "siren_fourier_features": (ci, [vp, vp, i64, ci, ci, vp, vp]),
+        "siren_sincos_f32": (ci, [vp, vp, vp, i64, ci, vp]),
+        "siren_last_error": (cstr, []),
+        "siren_version": (cstr, []),
+    }
+
+
+_SIGNATURES = _signatures()
+# Every symbol include/siren_mri_amd.h declares (checked by tests/test_native_abi.py).
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
 def _declare(lib):
-    P = ctypes.POINTER(SirenMLPDesc)
-    vp = ctypes.c_void_p
-    i64 = ctypes.c_int64
-    lib.siren_mlp_check.argtypes = [P]
-    lib.siren_mlp_check.restype = ctypes.c_int
-    lib.siren_mlp_saved_bytes.argtypes = [P]
-    lib.siren_mlp_saved_bytes.restype = i64
-    lib.siren_mlp_workspace_bytes.argtypes = [P]
-    lib.siren_mlp_workspace_bytes.restype = i64
-    lib.siren_mlp_forward.argtypes = [P, vp, vp, vp, i64, vp, i64, vp]
-    lib.siren_mlp_forward.restype = ctypes.c_int
-    lib.siren_mlp_backward.argtypes = [P, vp, vp, vp, i64, vp, i64,
-                                       ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-    lib.siren_mlp_backward.restype = ctypes.c_int
-    ci = ctypes.c_int
-    LP = ctypes.POINTER(SirenLossDesc)
-    lib.siren_mlp_loss_check.argtypes = [P, LP]
-    lib.siren_mlp_loss_check.restype = ci
-    lib.siren_mlp_forward_loss.argtypes = [P, LP, vp, vp, vp, i64, vp, i64, vp]
-    lib.siren_mlp_forward_loss.restype = ci
-    lib.siren_mlp_backward_ex.argtypes = [P, vp, vp, vp, vp, i64, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-    lib.siren_mlp_backward_ex.restype = ci
-    lib.siren_mlp64_saved_bytes.argtypes = [P]
-    lib.siren_mlp64_saved_bytes.restype = i64
-    lib.siren_mlp64_workspace_bytes.argtypes = [P]
-    lib.siren_mlp64_workspace_bytes.restype = i64
-    lib.siren_mlp64_forward.argtypes = [P, vp, vp, vp, i64, vp, i64, vp]
-    lib.siren_mlp64_forward.restype = ci
-    lib.siren_mlp64_backward.argtypes = [P, vp, vp, vp, i64, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-    lib.siren_mlp64_backward.restype = ci
-    HP = ctypes.POINTER(SirenHyperDesc)
-    lib.siren_hyper_saved_bytes.argtypes = [HP]
-    lib.siren_hyper_saved_bytes.restype = i64
-    lib.siren_hyper_workspace_bytes.argtypes = [HP]
-    lib.siren_hyper_workspace_bytes.restype = i64
-    lib.siren_hyper_forward.argtypes = [HP, vp, ctypes.POINTER(vp), vp, i64, vp]
-    lib.siren_hyper_forward.restype = ci
-    lib.siren_hyper_backward.argtypes = [HP, vp, ctypes.POINTER(vp), vp, i64, vp, i64, ctypes.POINTER(vp),
-                                         ctypes.POINTER(vp), vp, vp]
-    lib.siren_hyper_backward.restype = ci
-    lib.siren_enc_prep.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
-                                   ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp]
-    lib.siren_enc_prep.restype = ci
-    lib.siren_sumsq_workspace_bytes.argtypes = [i64]
-    lib.siren_sumsq_workspace_bytes.restype = i64
-    lib.siren_sumsq_forward.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), vp, vp, i64, vp]
-    lib.siren_sumsq_forward.restype = ci
-    lib.siren_sumsq_backward.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64), vp,
-                                         ctypes.POINTER(vp), vp]
-    lib.siren_sumsq_backward.restype = ci
-    lib.siren_jvp_saved_bytes.argtypes = [P, ci]
-    lib.siren_jvp_saved_bytes.restype = i64
-    lib.siren_jvp_workspace_bytes.argtypes = [P, ci]
-    lib.siren_jvp_workspace_bytes.restype = i64
-    lib.siren_jvp_forward.argtypes = [P, ci, vp, vp, vp, vp, i64, vp, i64, vp]
-    lib.siren_jvp_forward.restype = ci
-    lib.siren_jvp_forward_ex.argtypes = [P, ci, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]
-    lib.siren_jvp_forward_ex.restype = ci
-    lib.siren_jvp_backward.argtypes = [P, ci, vp, vp, vp, i64, vp, i64,
-                                       ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-    lib.siren_jvp_backward.restype = ci
-    lib.siren_jvp_backward_ex.argtypes = [P, ci, vp, vp, vp, i64, vp, i64,
-                                          ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp]
-    lib.siren_jvp_backward_ex.restype = ci
-    lib.siren_timing_enable.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.siren_timing_enable.restype = ctypes.c_int
-    lib.siren_timing_collect.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
-    lib.siren_timing_collect.restype = ctypes.c_int
-    lib.siren_timing_disable.argtypes = []
-    lib.siren_timing_disable.restype = None
-    lib.siren_config_set.argtypes = [ctypes.c_char_p, i64]
-    lib.siren_config_set.restype = ctypes.c_int
-    lib.siren_config_get.argtypes = [ctypes.c_char_p]
-    lib.siren_config_get.restype = i64
-    lib.siren_adam_step.argtypes = [ctypes.POINTER(SirenAdamDesc), vp]
-    lib.siren_adam_step.restype = ctypes.c_int
-    lib.siren_adam_num_blocks.argtypes = [ctypes.POINTER(SirenAdamDesc)]
-    lib.siren_adam_num_blocks.restype = ctypes.c_int64
-    f32 = ctypes.c_float
-    f64 = ctypes.c_double
-    lib.siren_adam_scalars.argtypes = [vp, f64, f64, f64, vp, vp]
-    lib.siren_adam_scalars.restype = ctypes.c_int
-    lib.siren_adam_scalars_table.argtypes = [vp, vp, i64, vp, vp]
-    lib.siren_adam_scalars_table.restype = ctypes.c_int
-    lib.siren_sse_workspace_bytes.argtypes = []
-    lib.siren_sse_workspace_bytes.restype = i64
-    lib.siren_conv_wrw_workspace_bytes.argtypes = [ci, ci, ci]
-    lib.siren_conv_wrw_workspace_bytes.restype = i64
-    lib.siren_conv_wrw_k5.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, i64, vp]
-    lib.siren_conv_wrw_k5.restype = ci
-    lib.siren_conv_fwd_k5.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]
-    lib.siren_conv_fwd_k5.restype = ci
-    lib.siren_conv_dgrad_k5_fused.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, i64, vp]
-    lib.siren_conv_dgrad_k5_fused.restype = ci
-    lib.siren_conv_fwd_k5_res.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    lib.siren_conv_fwd_k5_res.restype = ci
-    lib.siren_conv_check.argtypes = [ci, ci, ci, ci, ci, ci, ci]
-    lib.siren_conv_check.restype = ci
-    lib.siren_conv_fwd.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.siren_conv_fwd.restype = ci
-    lib.siren_conv_wrw_ws_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
-    lib.siren_conv_wrw_ws_bytes.restype = i64
-    lib.siren_conv_wrw.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, i64, vp]
-    lib.siren_conv_wrw.restype = ci
-    lib.siren_enc_workspace_bytes.argtypes = []
-    lib.siren_enc_workspace_bytes.restype = i64
-    lib.siren_enc_relu_bwd.argtypes = [vp, vp, vp, vp, vp, i64, ci, vp, i64, vp]
-    lib.siren_enc_relu_bwd.restype = ci
-    lib.siren_enc_bias_relu.argtypes = [vp, vp, i64, ci, vp]
-    lib.siren_enc_bias_relu.restype = ci
-    lib.siren_enc_res_fwd.argtypes = [vp, vp, vp, vp, i64, ci, vp]
-    lib.siren_enc_res_fwd.restype = ci
-    lib.siren_enc_res_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, ci, vp, i64, vp]
-    lib.siren_enc_res_bwd.restype = ci
-    lib.siren_enc_pixfc_fwd.argtypes = [vp, vp, vp, vp, vp, ci, i64, ci, vp, i64, vp]
-    lib.siren_enc_pixfc_fwd.restype = ci
-    lib.siren_enc_pixfc_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, i64, ci, vp, i64, vp]
-    lib.siren_enc_pixfc_bwd.restype = ci
-    lib.siren_sse_forward.argtypes = [vp, vp, vp, i64, i64, f32, vp, vp, vp, i64, vp]
-    lib.siren_sse_forward.restype = ctypes.c_int
-    lib.siren_sse_backward.argtypes = [vp, vp, i64, i64, vp, f32, vp, vp]
-    lib.siren_sse_backward.restype = ctypes.c_int
-    lib.siren_dc_forward.argtypes = [vp, vp, vp, i64, i64, ci, f32, vp, vp]
-    lib.siren_dc_forward.restype = ci
-    lib.siren_dc_backward.argtypes = [vp, vp, i64, i64, ci, f32, vp, vp]
-    lib.siren_dc_backward.restype = ci
-    lib.siren_kspace_sse_forward.argtypes = [vp, vp, vp, vp, vp, i64, i64, ci, f32, f32, vp, vp, vp, i64, vp]
-    lib.siren_kspace_sse_forward.restype = ci
-    lib.siren_kspace_sse_backward.argtypes = [vp, vp, vp, i64, i64, ci, f32, vp, f32, vp, vp]
-    lib.siren_kspace_sse_backward.restype = ci
-    KP = ctypes.POINTER(SirenKlossDesc)
-    lib.siren_kspace_loss_forward.argtypes = [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, i64, vp]
-    lib.siren_kspace_loss_forward.restype = ci
-    lib.siren_kspace_loss_backward.argtypes = [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, vp]
-    lib.siren_kspace_loss_backward.restype = ci
-    lib.siren_fourier_features.argtypes = [vp, vp, i64, ci, ci, vp, vp]
-    lib.siren_fourier_features.restype = ci
-    lib.siren_sincos_f32.argtypes = [vp, vp, vp, i64, ci, vp]
-    lib.siren_sincos_f32.restype = ci
-    lib.siren_last_error.argtypes = []
-    lib.siren_last_error.restype = ctypes.c_char_p
-    lib.siren_version.argtypes = []
-    lib.siren_version.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
 
 
 def load_library(path: str | None = None):
@@ -441,33 +316,52 @@ def stream_handle(device: torch.device) -> int:
     return torch._C._cuda_getCurrentRawStream(idx)
 
 
-_SSE_WS: dict = {}
+_WORKSPACES: dict = {}
+
+
+def _stream_workspace(kind: str, device) -> torch.Tensor:
+    """The zero-initialised `siren_<kind>_workspace_bytes()` buffer of (device, current stream), made once:
+    two launches that may run concurrently never share one."""
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        nbytes = getattr(lib(), f"siren_{kind}_workspace_bytes")()
+        ws = _WORKSPACES[key] = torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
+    return ws
 
 
 def sse_workspace(device) -> torch.Tensor:
     """The per-(device, stream) partial-sum / hand-off-counter workspace of the deterministic loss
-    reductions (siren_sse_workspace_bytes; zeroed once, left zeroed by every launch): two launches
-    that may run concurrently never share one."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _SSE_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(int(lib().siren_sse_workspace_bytes()), dtype=torch.uint8, device=device)
-        _SSE_WS[key] = ws
-    return ws
-
-
-_ENC_WS: dict = {}
+    reductions (siren_sse_workspace_bytes; zeroed once, left zeroed by every launch)."""
+    return _stream_workspace("sse", device)
 
 
 def enc_workspace(device) -> torch.Tensor:
-    """Per-(device, stream) workspace of the encoder passes' channel sums (siren_enc_workspace_bytes;
-    zeroed once, left zeroed by every launch)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    ws = _ENC_WS.get(key)
-    if ws is None:
-        ws = torch.zeros(int(lib().siren_enc_workspace_bytes()), dtype=torch.uint8, device=device)
-        _ENC_WS[key] = ws
-    return ws
+    """Per-(device, stream) workspace of the encoder passes (siren_enc_workspace_bytes; zeroed once). The
+    partial sums at its front are scratch that launches overwrite; only the ticket word behind them
+    (byte ENC_WS_FLOATS * 4) must stay zero, and every launch that takes it puts it back to zero."""
+    return _stream_workspace("enc", device)
+
+
+def _fill_desc(dims, weight_ptrs, bias_ptrs, ff_ptr, ff_in, *, w0, prec, outermost_linear, weights_batched, batch,
+               rows_per_batch) -> SirenMLPDesc:
+    d = SirenMLPDesc()
+    d.num_layers = len(dims) - 1
+    for i, v in enumerate(dims):
+        d.dims[i] = int(v)
+    d.outermost_linear = 1 if outermost_linear else 0
+    d.prec = int(prec)
+    d.weights_batched = 1 if weights_batched else 0
+    d.w0 = float(w0)
+    d.batch = int(batch)
+    d.rows_per_batch = int(rows_per_batch)
+    for l in range(d.num_layers):
+        d.weight[l] = weight_ptrs[l]
+        d.bias[l] = bias_ptrs[l]
+    if ff_ptr is not None:  # Fourier-feature input: x holds the raw coordinates
+        d.ff_B = ff_ptr
+        d.ff_in = int(ff_in)
+    return d
 
 
 def make_desc(dims, weights, biases, *, w0: float, prec: int, outermost_linear: bool,
@@ -475,46 +369,19 @@ def make_desc(dims, weights, biases, *, w0: float, prec: int, outermost_linear: 
     L = len(dims) - 1
     if not 2 <= L <= MAX_LAYERS:
         raise ValueError(f"siren_mri_amd: {L} linear layers outside [2, {MAX_LAYERS}]")
-    d = SirenMLPDesc()
-    d.num_layers = L
-    for i, v in enumerate(dims):
-        d.dims[i] = int(v)
-    d.outermost_linear = 1 if outermost_linear else 0
-    d.prec = int(prec)
-    d.weights_batched = 1 if weights_batched else 0
-    d.w0 = float(w0)
-    d.batch = int(batch)
-    d.rows_per_batch = int(rows_per_batch)
-    for l in range(L):
-        d.weight[l] = weights[l].data_ptr()
-        d.bias[l] = biases[l].data_ptr()
-    if ff_B is not None:  # Fourier-feature input: x holds the raw coordinates
-        d.ff_B = ff_B.data_ptr()
-        d.ff_in = int(ff_B.shape[0])
-    return d
+    return _fill_desc(dims, [w.data_ptr() for w in weights[:L]], [b.data_ptr() for b in biases[:L]],
+                      ff_B.data_ptr() if ff_B is not None else None, ff_B.shape[0] if ff_B is not None else 0,
+                      w0=w0, prec=prec, outermost_linear=outermost_linear, weights_batched=weights_batched,
+                      batch=batch, rows_per_batch=rows_per_batch)
 
 
 def describe_only(dims, *, prec: int, outermost_linear: bool = True, weights_batched: bool = False,
                   batch: int = 1, rows_per_batch: int = 1, w0: float = 30.0, ff_in: int = 0):
     """Descriptor with fake (aligned, non-null) pointers — for size queries and validation."""
     L = len(dims) - 1
-    d = SirenMLPDesc()
-    d.num_layers = L
-    for i, v in enumerate(dims):
-        d.dims[i] = int(v)
-    d.outermost_linear = 1 if outermost_linear else 0
-    d.prec = int(prec)
-    d.weights_batched = 1 if weights_batched else 0
-    d.w0 = float(w0)
-    d.batch = int(batch)
-    d.rows_per_batch = int(rows_per_batch)
-    for l in range(L):
-        d.weight[l] = 256 * (l + 1)
-        d.bias[l] = 256 * (l + 1) + 64
-    if ff_in:
-        d.ff_B = 256 * (L + 2)
-        d.ff_in = int(ff_in)
-    return d
+    return _fill_desc(dims, [256 * (l + 1) for l in range(L)], [256 * (l + 1) + 64 for l in range(L)],
+                      256 * (L + 2) if ff_in else None, ff_in, w0=w0, prec=prec, outermost_linear=outermost_linear,
+                      weights_batched=weights_batched, batch=batch, rows_per_batch=rows_per_batch)
 
 
 class KernelTimer:

@@ -1,0 +1,210 @@
+// rt_loss.hip — image and k-space losses, data consistency, Fourier features and the sin/cos probe
+// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip). Included by siren_runtime.hip.
+namespace {
+
+// one launch of KERNEL<kind> (kind checked by kloss_check)
+#define KLOSS_LAUNCH(KERNEL, kind, blocks, stream, a)                                                   \
+  do {                                                                                                   \
+    switch (kind) {                                                                                      \
+      case SIREN_KLOSS_ASINH: hipLaunchKernelGGL(KERNEL<KL_ASINH>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_CUBIC: hipLaunchKernelGGL(KERNEL<KL_CUBIC>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_SMAPE: hipLaunchKernelGGL(KERNEL<KL_SMAPE>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
+      case SIREN_KLOSS_L1: hipLaunchKernelGGL(KERNEL<KL_L1>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;       \
+      case SIREN_KLOSS_PERP: hipLaunchKernelGGL(KERNEL<KL_PERP>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;   \
+      default: hipLaunchKernelGGL(KERNEL<KL_LOG>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;                  \
+    }                                                                                                    \
+  } while (0)
+
+// the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
+int kloss_check(const char* what, int kind, const siren_kloss_desc* desc, const float* k0, const float* mask,
+                int64_t batch, int64_t npix, int channels) {
+  if (kind < 0 || kind >= SIREN_KLOSS_KINDS)
+    return fail(SIREN_EINVAL, "%s: kind %d outside [0, %d)", what, kind, (int)SIREN_KLOSS_KINDS);
+  if (!desc) return fail(SIREN_EINVAL, "%s: null descriptor", what);
+  if (channels < 1 || channels > KL_MAXC)
+    return fail(SIREN_EINVAL, "%s: channels %d outside [1, %d]", what, channels, KL_MAXC);
+  if ((kind == SIREN_KLOSS_PERP || kind == SIREN_KLOSS_LOG) && channels != 2)
+    return fail(SIREN_EINVAL, "%s: kind %d (%s) takes complex pixels, channels == 2, got %d", what, kind,
+                kind == SIREN_KLOSS_PERP ? "perp" : "log", channels);
+  if ((!k0) != (!mask)) return fail(SIREN_EINVAL, "%s: k0 and mask go together (data consistency)", what);
+  if (batch < 0 || npix < 0)
+    return fail(SIREN_EINVAL, "%s: bad sizes (batch=%lld, npix=%lld)", what, (long long)batch, (long long)npix);
+  return SIREN_OK;
+}
+
+KlossArgs kloss_args(const siren_kloss_desc* d, const float* pred, const float* k0, const float* mask,
+                     const float* tgt, int64_t batch, int64_t npix, int channels, float noise) {
+  KlossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.k0 = k0;
+  a.mask = mask;
+  a.tgt = tgt;
+  a.batch = batch;
+  a.npix = npix;
+  a.C = channels;
+  a.noise = noise;
+  a.weight = d->weight;
+  a.eps = d->eps;
+  a.scale = d->scale;
+  a.divisor = d->divisor;
+  a.mag_weight = d->mag_weight;
+  a.phase_weight = d->phase_weight;
+  return a;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t siren_sse_workspace_bytes(void) { return (int64_t)SSE_MAX_BLOCKS * 4 + 256; }
+
+int siren_sse_forward(const float* pred, const float* tgt, const float* mask, int64_t n, int64_t mask_n,
+                      float weight, float* d, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
+  if (n < 0 || !loss || (n > 0 && (!pred || !tgt || !d)) || (mask && mask_n <= 0))
+    return fail(SIREN_EINVAL, "sse_forward: bad arguments (n=%lld, mask_n=%lld)", (long long)n, (long long)mask_n);
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "sse_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  SseFwdArgs a;
+  a.pred = pred;
+  a.tgt = tgt;
+  a.mask = mask;
+  a.d = d;
+  a.loss = loss;
+  a.partial = (float*)workspace;
+  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
+  a.n = n;
+  a.mask_n = mask ? mask_n : 1;
+  a.weight = weight;
+  // 16 elements per thread: few enough blocks that the hand-off counter (one agent-scope add per
+  // block, all on one address) stays off the critical path (262144 elements: 64 blocks)
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(SSE_MAX_BLOCKS, cdiv(n, 16 * SSE_THREADS)));
+  hipLaunchKernelGGL(sse_fwd_kernel, dim3(blocks), dim3(SSE_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("sse_forward");
+}
+
+int siren_sse_backward(const float* d, const float* mask, int64_t n, int64_t mask_n, const float* g, float scale,
+                       float* out, void* stream) {
+  if (n < 0 || (n > 0 && (!d || !g || !out)) || (mask && mask_n <= 0))
+    return fail(SIREN_EINVAL, "sse_backward: bad arguments (n=%lld, mask_n=%lld)", (long long)n, (long long)mask_n);
+  if (n == 0) return SIREN_OK;
+  SseBwdArgs a;
+  a.d = d;
+  a.mask = mask;
+  a.g = g;
+  a.out = out;
+  a.n = n;
+  a.mask_n = mask ? mask_n : 1;
+  a.scale = scale;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(n, 4 * SSE_THREADS)));
+  hipLaunchKernelGGL(sse_bwd_kernel, dim3(blocks), dim3(SSE_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("sse_backward");
+}
+
+int siren_dc_forward(const float* pred, const float* k0, const float* mask, int64_t batch, int64_t npix,
+                     int channels, float noise, float* out, void* stream) {
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!pred || !k0 || !mask || !out)))
+    return fail(SIREN_EINVAL, "dc_forward: bad arguments (batch=%lld, npix=%lld, channels=%d)", (long long)batch,
+                (long long)npix, channels);
+  if (batch * npix == 0) return SIREN_OK;
+  DcArgs a{pred, k0, mask, out, batch, npix, channels, noise, 0};
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KS_THREADS)));
+  hipLaunchKernelGGL(dc_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("dc_forward");
+}
+
+int siren_dc_backward(const float* g, const float* mask, int64_t batch, int64_t npix, int channels, float noise,
+                      float* dpred, void* stream) {
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!g || !mask || !dpred)))
+    return fail(SIREN_EINVAL, "dc_backward: bad arguments");
+  if (batch * npix == 0) return SIREN_OK;
+  DcArgs a{g, nullptr, mask, dpred, batch, npix, channels, noise, 1};
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KS_THREADS)));
+  hipLaunchKernelGGL(dc_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("dc_backward");
+}
+
+int siren_kspace_sse_forward(const float* pred, const float* k0, const float* mask, const float* tgt,
+                             const float* hf, int64_t batch, int64_t npix, int channels, float noise, float weight,
+                             float* d, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || !loss || (!k0) != (!mask) ||
+      (batch * npix > 0 && (!pred || !tgt || !d)))
+    return fail(SIREN_EINVAL, "kspace_sse_forward: bad arguments (batch=%lld, npix=%lld, channels=%d)",
+                (long long)batch, (long long)npix, channels);
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "kspace_sse_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  KsseFwdArgs a{pred, k0, mask, tgt, hf, d, loss, (float*)workspace,
+                (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4), batch, npix, channels, noise, weight};
+  // 8 coordinates per thread: few blocks for the hand-off counter (32 x 16384 coordinates: 256)
+  const unsigned blocks =
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(KS_MAX_BLOCKS, cdiv(batch * npix, 8 * KS_THREADS)));
+  hipLaunchKernelGGL(ksse_fwd_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("kspace_sse_forward");
+}
+
+int siren_kspace_sse_backward(const float* d, const float* mask, const float* hf, int64_t batch, int64_t npix,
+                              int channels, float noise, const float* g, float scale, float* dpred, void* stream) {
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!d || !g || !dpred)))
+    return fail(SIREN_EINVAL, "kspace_sse_backward: bad arguments");
+  if (batch * npix == 0) return SIREN_OK;
+  KsseBwdArgs a{d, mask, hf, g, dpred, batch, npix, channels, noise, scale};
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KS_THREADS)));
+  hipLaunchKernelGGL(ksse_bwd_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("kspace_sse_backward");
+}
+
+int siren_kspace_loss_forward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                              const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                              float noise, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = kloss_check("kspace_loss_forward", kind, desc, k0, mask, batch, npix, channels)) return rc;
+  if (!loss || (batch * npix > 0 && (!pred || !tgt))) return fail(SIREN_EINVAL, "kspace_loss_forward: null pointer");
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "kspace_loss_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  static_assert(KL_MAX_BLOCKS == SSE_MAX_BLOCKS, "the hand-off's slots are siren_sse_workspace_bytes()'s");
+  KlossArgs a = kloss_args(desc, pred, k0, mask, tgt, batch, npix, channels, noise);
+  a.out = loss;
+  a.partial = (float*)workspace;
+  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
+  // 8 coordinates per thread, as kspace_sse_forward: few blocks for the hand-off counter
+  const unsigned blocks =
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(KL_MAX_BLOCKS, cdiv(batch * npix, 8 * KL_THREADS)));
+  KLOSS_LAUNCH(kloss_fwd_kernel, kind, blocks, (hipStream_t)stream, a);
+  return check_launch("kspace_loss_forward");
+}
+
+int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
+                               const float* mask, const float* tgt, int64_t batch, int64_t npix, int channels,
+                               float noise, const float* g, float* dpred, void* stream) {
+  if (int rc = kloss_check("kspace_loss_backward", kind, desc, k0, mask, batch, npix, channels)) return rc;
+  if (batch * npix > 0 && (!pred || !tgt || !g || !dpred))
+    return fail(SIREN_EINVAL, "kspace_loss_backward: null pointer");
+  if (batch * npix == 0) return SIREN_OK;
+  KlossArgs a = kloss_args(desc, pred, k0, mask, tgt, batch, npix, channels, noise);
+  a.g = g;
+  a.out = dpred;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KL_THREADS)));
+  KLOSS_LAUNCH(kloss_bwd_kernel, kind, blocks, (hipStream_t)stream, a);
+  return check_launch("kspace_loss_backward");
+}
+
+int siren_fourier_features(const float* x, const float* B, int64_t rows, int cin, int m, float* out, void* stream) {
+  if (rows < 0 || cin < 1 || m < 1 || (rows > 0 && (!x || !B || !out)))
+    return fail(SIREN_EINVAL, "fourier_features: bad arguments (rows=%lld, cin=%d, m=%d)", (long long)rows, cin, m);
+  if (rows == 0) return SIREN_OK;
+  FourierArgs a{x, B, out, rows, cin, m};
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(rows * m, KS_THREADS)));
+  hipLaunchKernelGGL(fourier_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("fourier_features");
+}
+
+int siren_sincos_f32(const float* x, float* s, float* c, int64_t n, int impl, void* stream) {
+  if (n < 0 || (impl != 0 && impl != 1) || (n > 0 && (!x || !s || !c)))
+    return fail(SIREN_EINVAL, "sincos_f32: bad arguments (n=%lld, impl=%d)", (long long)n, impl);
+  if (n == 0) return SIREN_OK;
+  hipLaunchKernelGGL(sincos_probe_kernel, dim3(grid1d(n, 4096)), dim3(256), 0, (hipStream_t)stream, x, s, c, n, impl);
+  return check_launch("sincos_f32");
+}
+
+}  // extern "C"

@@ -99,6 +99,42 @@ def test_config_options():
     assert "unknown option" in _native.last_error()
 
 
+# name -> (min, max, default) of every integer option of siren_config_set / siren_config_get
+_ON = ("fused_forward", "fused_backward", "ring_output_fusion", "fused_forward_pipe", "fused_forward_reg", "dw_ring",
+       "dx_ring", "pair_tail_reduce", "jvp_adj", "f32_rows", "jvp_tan", "jvp_tn2", "pair_ring")
+_OFF = ("fuse_output_layer", "freg_magic", "bwd_ring", "dx_stagger", "debug_keep_p0")
+OPTIONS = {**{k: (0, 1, 1) for k in _ON}, **{k: (0, 1, 0) for k in _OFF},
+           "debug_pair_roles": (0, 3, 3), "wrw_dma": (0, 3, 2), "conv_dma": (0, 2, 2), "debug_fwd_skip": (0, 31, 0)}
+
+
+@pytest.mark.parametrize("key", sorted(OPTIONS))
+def test_option_table_row(key):
+    """Every option reads back its default, round-trips each value of its range, and refuses the
+    values just outside it with "unknown option", leaving the value as it was."""
+    lib = _native.load_library()
+    lo, hi, default = OPTIONS[key]
+    k = key.encode()
+    assert lib.siren_config_get(k) == default
+    try:
+        for v in range(lo, hi + 1):
+            assert lib.siren_config_set(k, v) == 0, _native.last_error()
+            assert lib.siren_config_get(k) == v
+            for bad in (lo - 1, hi + 1):
+                assert lib.siren_config_set(k, bad) != 0
+                assert "unknown option" in _native.last_error()
+                assert lib.siren_config_get(k) == v
+    finally:
+        assert lib.siren_config_set(k, default) == 0
+    assert lib.siren_config_get(k) == default
+
+
+@pytest.mark.parametrize("key", [b"debug_ring_profile", b"debug_fused_profile"])
+def test_pointer_options_are_set_only(key):
+    lib = _native.load_library()
+    assert lib.siren_config_set(key, 0) == 0
+    assert lib.siren_config_get(key) == -1
+
+
 def test_empty_input_rejected():
     lib = _native.load_library()
     d = _desc([2, 64, 1], rows_per_batch=0)
