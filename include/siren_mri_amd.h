@@ -160,6 +160,20 @@ int siren_mlp_backward_ex(const siren_mlp_desc* d, const float* x, const float* 
                           const void* saved, int64_t saved_bytes, void* workspace,
                           int64_t workspace_bytes, float* const* dweight, float* const* dbias,
                           float* dx, void* stream);
+/*
+ * The launch plan of siren_mlp_backward for this descriptor under the current options, as text:
+ * one line per launch in launch order (reductions and the copy of a misaligned x included), each
+ *   <kernel symbol with its template arguments> class=<SIREN_KCLASS_*, 0: none> layer=<l>
+ *   grid=(x,y,z) block=<threads> [slab=<part|part2|partL|partB>[+..] nsplit=<n>[+..]]
+ *   [p_vec=<0|1>: the wide first layer's weight gradient reads x rows as 16-byte vectors]
+ *   [reduce=<own|next_pair|flush>]
+ * after one "# ..." line naming the output-layer and first-layer forms (the copy is the line
+ * "hipMemcpyAsync ... grid=(0,0,0) block=0"). flags: bit 0 an input
+ * gradient is wanted, bit 1 x is 16-byte aligned, bit 2 dy is. Writes at most cap bytes to out
+ * (NUL-terminated when cap > 0) and returns the bytes needed, NUL included, or -1 with
+ * siren_last_error set. Touches no device: it is the plan object siren_mlp_backward walks, printed.
+ */
+int64_t siren_mlp_backward_plan(const siren_mlp_desc* d, int flags, char* out, int64_t cap);
 
 /*
  * Analytic spatial derivatives of the SIREN output w.r.t. its input (tangent streams carried
@@ -220,7 +234,7 @@ int siren_jvp_backward_ex(const siren_mlp_desc* d, int order, const float* x, co
 #define SIREN_KCLASS_DX_GEMM 2  /* hidden-layer input-gradient GEMM + cos-weighted epilogue */
 #define SIREN_KCLASS_DW_GEMM 3  /* hidden-layer weight-gradient split-K GEMM               */
 #define SIREN_KCLASS_FWD_FUSED 4 /* whole forward in one kernel (bf16, narrow in/out layers) */
-#define SIREN_KCLASS_BWD_FUSED 5 /* a middle layer's input + weight gradients in one kernel   */
+#define SIREN_KCLASS_BWD_FUSED 5 /* reserved (formerly bwd_ring): no kernel launches in it     */
 #define SIREN_KCLASS_DX_RING 6   /* dx_ring_bf16_kernel, middle layer                         */
 #define SIREN_KCLASS_DW_RING 7   /* dw_ring_bf16_kernel, middle layer                         */
 #define SIREN_KCLASS_DX_RING_BOT 8 /* dx_ring_bf16_kernel with the first layer folded in      */
@@ -530,8 +544,6 @@ int siren_sincos_f32(const float* x, float* s, float* c, int64_t n, int impl, vo
  *                    ring); 0: the LDS-staged fused forward below.
  *   "fused_forward_pipe"  1 (default): the LDS-staged fused forward overlaps one half-tile's MFMA
  *                    work with the other's epilogue; 0: the sequential single-kernel forward.
- *   "bwd_ring"       0 (default), 1: middle 256x256 bf16 layers compute both gradients in one
- *                    kernel (dZ and P read once); 0: separate input/weight-gradient kernels.
  *   "dw_ring"        1 (default): 256x256 bf16 weight-gradient layers use the ring kernel
  *                    (one full 256x256 partial per workgroup); 0: 128x128-tile split-K kernel.
  *   "pair_ring"      1 (default): a 256x256 bf16 layer whose two gradients both run on the ring

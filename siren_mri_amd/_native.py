@@ -28,7 +28,7 @@ KCLASS_FWD_GEMM = 1
 KCLASS_DX_GEMM = 2
 KCLASS_DW_GEMM = 3
 KCLASS_FWD_FUSED = 4
-KCLASS_BWD_FUSED = 5
+KCLASS_BWD_FUSED = 5  # reserved (formerly bwd_ring): nothing launches in it
 KCLASS_DX_RING = 6
 KCLASS_DW_RING = 7
 KCLASS_DX_RING_BOT = 8
@@ -177,6 +177,7 @@ def _signatures():
         "siren_mlp_loss_check": (ci, [P, LP]),
         "siren_mlp_forward_loss": (ci, [P, LP, vp, vp, vp, i64, vp, i64, vp]),
         "siren_mlp_backward_ex": (ci, [P, vp, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]),
+        "siren_mlp_backward_plan": (i64, [P, ci, cstr, i64]),
         "siren_mlp64_saved_bytes": (i64, [P]),
         "siren_mlp64_workspace_bytes": (i64, [P]),
         "siren_mlp64_forward": (ci, fwd),

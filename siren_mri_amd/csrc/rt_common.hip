@@ -51,8 +51,8 @@ Geo geo_of(const siren_mlp_desc* d) {
 // Execution options (siren_config_set / siren_config_get). The launch code reads these plain
 // globals; kOptions below is the one list of their names, ranges and defaults, and writes the
 // defaults into them when the library is loaded.
-int g_fused_forward, g_fused_backward, g_ring_top, g_fuse_top, g_fwd_pipe, g_fwd_reg, g_freg_magic, g_bwd_ring,
-    g_dx_ring, g_dw_ring, g_pair_ring, g_pair_roles, g_dx_stagger, g_tail_reduce, g_jvp_adj, g_jvp_tan, g_jvp_tn2,
+int g_fused_forward, g_fused_backward, g_ring_top, g_fuse_top, g_fwd_pipe, g_fwd_reg, g_freg_magic, g_dx_ring,
+ g_dw_ring, g_pair_ring, g_pair_roles, g_dx_stagger, g_tail_reduce, g_jvp_adj, g_jvp_tan, g_jvp_tn2,
     g_f32_rows, g_wrw_dma, g_conv_dma, g_keep_p0, g_fwd_dbg;
 
 struct Option {
@@ -65,7 +65,6 @@ const Option kOptions[] = {
     {"fused_backward", &g_fused_backward, 0, 1, 1},  // bf16 backward: first / output layer folded into their neighbours
     {"fuse_output_layer", &g_fuse_top, 0, 1, 0},     // output-layer fusion into the tiled kernels: slower than last_bwd, off
     {"ring_output_fusion", &g_ring_top, 0, 1, 1},    // output layer folded into the top 256x256 layer's ring kernels
-    {"bwd_ring", &g_bwd_ring, 0, 1, 0},  // middle 256x256 layers in one ring kernel: measured slower (179 vs 145 us)
     {"fused_forward_pipe", &g_fwd_pipe, 0, 1, 1},  // fused forward: half-tile MFMA/VALU pipelined kernel
     {"fused_forward_reg", &g_fwd_reg, 0, 1, 1},    // fused forward: activations resident in registers (siren_fwdreg.hip)
     // its hidden layers in the magic epilogue form where the weights allow it: off by default — the
@@ -107,6 +106,9 @@ const Option* find_option(const char* key) {
 long long* g_ring_prof = nullptr;   // debug_ring_profile: pair_ring segment cycle counters, one block per launch
 int g_ring_prof_n = 0;              // (launches counted since debug_ring_profile was set)
 long long* g_fused_prof = nullptr;  // debug_fused_profile: per-workgroup phase cycle counters of the fused forward
+inline long long* ring_profile_next() {  // the next pair launch's counter block (null: profiling is off)
+  return g_ring_prof ? g_ring_prof + (int64_t)(g_ring_prof_n++) * 256 * 8 * RING_NPROF : nullptr;
+}
 
 // The buffer checks of the stack entry points (siren_mlp_*, siren_jvp_*): the saved buffer (a backward
 // pass requires it, a forward pass may go without) and the workspace hold what the layout needs.

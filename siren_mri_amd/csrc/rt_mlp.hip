@@ -221,39 +221,14 @@ Layout layout_of(const siren_mlp_desc* d) {
   return lo;
 }
 
+inline int64_t reduce_blocks(int64_t nb, int64_t slab) { return cdiv(nb * slab, 128); }
 int launch_reduce(const float* part, int64_t nsplit, int64_t sstride, int64_t nb, int64_t slab,
                   int64_t n_first, float* out0, float* out1, hipStream_t st) {
   const int64_t total = nb * slab;
-  hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)cdiv(total, 128)), dim3(256), 0, st, part,
+  hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)reduce_blocks(nb, slab)), dim3(256), 0, st, part,
                      (int)nsplit, sstride, (int)total, (int)slab, (int)n_first, out0, out1);
   return check_launch("reduce");
 }
-
-// Up to REDUCE_MAXSEG reductions (same arguments as launch_reduce) in one launch.
-struct ReduceList {
-  ReduceMultiArgs a;
-  int64_t blocks = 0;
-  ReduceList() { memset(&a, 0, sizeof(a)); }
-  void add(const float* part, int64_t nsplit, int64_t sstride, int64_t nb, int64_t slab, int64_t n_first, float* out0,
-           float* out1) {
-    ReduceSeg& g = a.seg[a.nseg++];
-    g.part = part;
-    g.nsplit = (int)nsplit;
-    g.split_stride = sstride;
-    g.total = (int)(nb * slab);
-    g.slab = (int)slab;
-    g.n_first = (int)n_first;
-    g.out0 = out0;
-    g.out1 = out1;
-    g.blocks = (int)cdiv(nb * slab, 128);
-    blocks += g.blocks;
-  }
-  int launch(hipStream_t st) {
-    if (a.nseg == 0) return SIREN_OK;
-    hipLaunchKernelGGL(reduce_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
-    return check_launch("reduce_multi");
-  }
-};
 
 // Convert every MFMA layer's weights (bf16 copy + transpose) into `dst` in one launch.
 template <int PREC>
@@ -278,177 +253,170 @@ int prep_weights(const siren_mlp_desc* d, const Geo& g, const Layout& lo, char* 
   return check_launch("prep_weights");
 }
 
-template <int PREC, int IT, int MAXO>
-void launch_last_fwd(const LastFwdArgs& a, int64_t nb, hipStream_t st) {
-  if (a.lloss) {  // fused image loss: at most SSE_MAX_BLOCKS workgroups (the hand-off's slots)
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(a.rows_per_batch, 8),
-                                                                        std::max<int64_t>(1, SSE_MAX_BLOCKS / nb)));
-    hipLaunchKernelGGL((last_fwd_kernel<PREC, IT, MAXO, true>), dim3(gx, (unsigned)nb), dim3(256), 0, st, a);
-    return;
-  }
+// Elements between the weight sets of a parameter of n elements (0: shared weights).
+inline int64_t bstride(const siren_mlp_desc* d, int64_t n) { return d->weights_batched ? n : 0; }
+
+// A kernel and the name a profiler prints for it. Every table below lists exactly the forms the
+// library instantiates: adding an entry adds a kernel to the code object.
+template <class... Args>
+struct Kernel {
+  void (*fn)(Args...);
+  const char* sym;
+};
+#define SIREN_K(...) {__VA_ARGS__, "siren::" #__VA_ARGS__}
+// the forms of a VALU layer kernel for 256, 512 and 1024 features per row (template argument IT)
+#define SIREN_IT(K, P, ...) {SIREN_K(K<P, 1, __VA_ARGS__>), SIREN_K(K<P, 2, __VA_ARGS__>), SIREN_K(K<P, 4, __VA_ARGS__>)}
+inline int it_index(int F) { return F <= 256 ? 0 : F <= 512 ? 1 : 2; }
+// the forms of a first-layer fusion for C = 1..4 inputs: M(C, ...) names one
+#define SIREN_C4(M, ...) {M(1, __VA_ARGS__), M(2, __VA_ARGS__), M(3, __VA_ARGS__), M(4, __VA_ARGS__)}
+
+template <class... Args>
+int launch_kernel(const Kernel<Args...>& k, dim3 grid, unsigned block, int kclass, const char* what, hipStream_t st,
+           const Args&... a) {
+  tmark_begin(kclass, st);
+  hipLaunchKernelGGL(k.fn, grid, dim3(block), 0, st, a...);
+  tmark_end(kclass, st);
+  return check_launch(what);
+}
+
+// The fused-loss fields of a forward kernel's arguments (FwdRegArgs, LastFwdArgs).
+template <class Args>
+void set_loss(Args& a, const siren_loss_desc& L) {
+  a.ltgt = L.target;
+  a.lk0 = L.k0;
+  a.lmask = L.mask;
+  a.lhf = L.hf;
+  a.ldc = L.y_dc;
+  a.ldy = L.dy;
+  a.lloss = L.loss;
+  a.lpart = (float*)L.loss_workspace;
+  a.lcounter = (unsigned*)((char*)L.loss_workspace + SSE_MAX_BLOCKS * 4);
+  a.lnoise = L.noise;
+  a.lweight = L.weight;
+}
+
+// Output layer forward (VALU), [prec][fused loss][O > 2][it_index].
+int launch_last_fwd(int prec, const LastFwdArgs& a, int64_t nb, hipStream_t st) {
+  static const Kernel<LastFwdArgs> k[2][2][2][3] = {
+      {{SIREN_IT(last_fwd_kernel, 0, 2, false), SIREN_IT(last_fwd_kernel, 0, 8, false)},
+       {SIREN_IT(last_fwd_kernel, 0, 2, true), SIREN_IT(last_fwd_kernel, 0, 8, true)}},
+      {{SIREN_IT(last_fwd_kernel, 1, 2, false), SIREN_IT(last_fwd_kernel, 1, 8, false)},
+       {SIREN_IT(last_fwd_kernel, 1, 2, true), SIREN_IT(last_fwd_kernel, 1, 8, true)}}};
+  // fused image loss: at most SSE_MAX_BLOCKS workgroups (the hand-off's slots)
+  const int64_t cap = a.lloss ? SSE_MAX_BLOCKS : 4096;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(a.rows_per_batch, 8),
-                                                                      std::max<int64_t>(1, 4096 / nb)));
-  hipLaunchKernelGGL((last_fwd_kernel<PREC, IT, MAXO>), dim3(gx, (unsigned)nb), dim3(256), 0, st, a);
-}
-
-template <int PREC>
-int dispatch_last_fwd(const LastFwdArgs& a, int64_t nb, hipStream_t st) {
-  const int it = (int)cdiv(a.F, 256);
-  if (a.O <= 2) {
-    if (it == 1) launch_last_fwd<PREC, 1, 2>(a, nb, st);
-    else if (it == 2) launch_last_fwd<PREC, 2, 2>(a, nb, st);
-    else launch_last_fwd<PREC, 4, 2>(a, nb, st);
-  } else {
-    if (it == 1) launch_last_fwd<PREC, 1, 8>(a, nb, st);
-    else if (it == 2) launch_last_fwd<PREC, 2, 8>(a, nb, st);
-    else launch_last_fwd<PREC, 4, 8>(a, nb, st);
-  }
-  return check_launch("last_fwd");
-}
-
-template <int PREC>
-int dispatch_last_bwd(const LastBwdArgs& a, int64_t nsplit, int64_t nb, hipStream_t st) {
-  const int it = (int)cdiv(a.F, 256);
-  dim3 grid((unsigned)nsplit, (unsigned)nb);
-  if (a.O <= 2) {
-    if (it == 1) hipLaunchKernelGGL((last_bwd_kernel<PREC, 1, 2>), grid, dim3(256), 0, st, a);
-    else if (it == 2) hipLaunchKernelGGL((last_bwd_kernel<PREC, 2, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((last_bwd_kernel<PREC, 4, 2>), grid, dim3(256), 0, st, a);
-  } else {
-    if (it == 1) hipLaunchKernelGGL((last_bwd_kernel<PREC, 1, 8>), grid, dim3(256), 0, st, a);
-    else if (it == 2) hipLaunchKernelGGL((last_bwd_kernel<PREC, 2, 8>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((last_bwd_kernel<PREC, 4, 8>), grid, dim3(256), 0, st, a);
-  }
-  return check_launch("last_bwd");
-}
-
-template <int PREC>
-int dispatch_first_bwd(const FirstBwdArgs& a, int64_t nsplit, int64_t nb, hipStream_t st) {
-  const int it = (int)cdiv(a.F, 256);
-  dim3 grid((unsigned)nsplit, (unsigned)nb);
-  if (a.ffB) {  // Fourier-feature input: the MFMA weight-gradient kernel forms the features itself
-    if (!(PREC == kPrecBF16 && a.F == 256 && a.C > 4 && a.rows_per_split % 32 == 0 && !a.dx))
-      return fail(SIREN_EINVAL, "fourier input: first-layer backward needs the bf16 wide MFMA path and no dx");
-    hipLaunchKernelGGL(first_bwd_wide_mfma_kernel, grid, dim3(256), 0, st, a);
-    return check_launch("first_bwd_wide_mfma (fourier input)");
-  }
-  if (a.C <= 4) {
-    if (it == 1) hipLaunchKernelGGL((first_bwd_kernel<PREC, 1, 4>), grid, dim3(256), 0, st, a);
-    else if (it == 2) hipLaunchKernelGGL((first_bwd_kernel<PREC, 2, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((first_bwd_kernel<PREC, 4, 4>), grid, dim3(256), 0, st, a);
-  } else if (a.F <= 256 && (!a.dx || (PREC == kPrecBF16 && a.F == 256))) {
-    // weight gradient without dx; the input gradient (bf16 mode) as its own MFMA launch
-    FirstBwdArgs aw = a;
-    aw.dx = nullptr;
-    if (PREC == kPrecBF16 && a.F == 256 && a.rows_per_split % 32 == 0)
-      hipLaunchKernelGGL(first_bwd_wide_mfma_kernel, grid, dim3(256), 0, st, aw);
-    else if (a.C == 16) hipLaunchKernelGGL((first_bwd_wide_kernel<PREC, 16>), grid, dim3(256), 0, st, aw);
-    else hipLaunchKernelGGL((first_bwd_wide_kernel<PREC, 0>), grid, dim3(256), 0, st, aw);
-    if (a.dx) {
-      int rc = check_launch("first_bwd_wide");
-      if (rc) return rc;
-      const int64_t ntile = cdiv(a.rows_per_batch, 32);
-      hipLaunchKernelGGL(first_dx_wide_kernel, dim3((unsigned)cdiv(ntile, 4), (unsigned)nb), dim3(256), 0, st, a);
-    }
-  } else {
-    if (it == 1) hipLaunchKernelGGL((first_bwd_kernel<PREC, 1, 16>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((first_bwd_kernel<PREC, 2, 16>), grid, dim3(256), 0, st, a);
-  }
-  return check_launch("first_bwd");
+                                                                      std::max<int64_t>(1, cap / nb)));
+  return launch_kernel(k[prec][a.lloss ? 1 : 0][a.O <= 2 ? 0 : 1][it_index(a.F)], dim3(gx, (unsigned)nb), 256, 0,
+                "last_fwd", st, a);
 }
 
 // One hidden-layer GEMM launch (MODE_FWD or MODE_DX). Persistent grid: one 512-thread workgroup
 // per CU (~131 KB LDS each), spread over weight sets and 256-column tiles.
-dim3 nt_grid(const NTArgs& a, int64_t nb, int prec) {
-  const int ntn = (int)cdiv(a.N, 256);
-  const int kmax = a.K <= 256 ? 256 : 512;  // siren_mlp_check bounds K by 512 (bf16) / 256 (f32)
+dim3 nt_grid(int64_t rows, int K, int N, int64_t nb, int prec) {
+  const int ntn = (int)cdiv(N, 256);
+  const int kmax = K <= 256 ? 256 : 512;  // siren_mlp_check bounds K by 512 (bf16) / 256 (f32)
   const int bm = prec == kPrecBF16 ? 64 * 256 / kmax : 32;
-  const int64_t tiles = cdiv(a.rows_per_batch, bm);
+  const int64_t tiles = cdiv(rows, bm);
   const int64_t per = std::max<int64_t>(1, 256 / std::max<int64_t>(1, nb * ntn));
   return dim3((unsigned)std::min<int64_t>(tiles, per), (unsigned)nb, (unsigned)ntn);
 }
 
-dim3 ring_grid(const NTArgs& a, int64_t nb) {
-  const int64_t tiles = cdiv(a.rows_per_batch, RING_BM);
+dim3 ring_grid(int64_t rows, int64_t nb) {
+  const int64_t tiles = cdiv(rows, RING_BM);
   const int64_t per = std::max<int64_t>(1, 256 / nb);
   return dim3((unsigned)std::min<int64_t>(tiles, per), (unsigned)nb, 1);
 }
 
-// Bottom 256x256 input-gradient layer with the first layer folded in (dx_ring_bf16_kernel BOTC).
-int launch_dx_ring_bot(const NTArgs& a, int64_t nb, int C, bool dxout, bool rec, int kclass, hipStream_t st) {
-  const dim3 grid = ring_grid(a, nb);
-  tmark_begin(kclass, st);
-#define SIREN_RING_BOT(CC)                                                                              \
-  if (rec) {                                                                                             \
-    if (dxout) hipLaunchKernelGGL((dx_ring_bf16_kernel<CC, true, true>), grid, dim3(512), 0, st, a);     \
-    else hipLaunchKernelGGL((dx_ring_bf16_kernel<CC, false, true>), grid, dim3(512), 0, st, a);          \
-  } else {                                                                                               \
-    if (dxout) hipLaunchKernelGGL((dx_ring_bf16_kernel<CC, true>), grid, dim3(512), 0, st, a);           \
-    else hipLaunchKernelGGL((dx_ring_bf16_kernel<CC, false>), grid, dim3(512), 0, st, a);                \
-  }
-  switch (C) {
-    case 1: SIREN_RING_BOT(1) break;
-    case 2: SIREN_RING_BOT(2) break;
-    case 3: SIREN_RING_BOT(3) break;
-    default: SIREN_RING_BOT(4) break;
-  }
-#undef SIREN_RING_BOT
-  tmark_end(kclass, st);
-  return check_launch("dx_ring first-layer");
+// The tiled GEMM kernels, [MODE_*][K > 256]; the bf16 input gradient also with the output layer
+// (top) and / or the first layer (bot) folded in (both at once is never planned: a stack with one
+// hidden layer takes one fusion only).
+const Kernel<NTArgs>& nt_kernel(int prec, int mode, int K, bool top = false, bool bot = false) {
+  static const Kernel<NTArgs> f32[4][2] = {{SIREN_K(nt_f32_kernel<0, 256>), SIREN_K(nt_f32_kernel<0, 512>)},
+                                           {SIREN_K(nt_f32_kernel<1, 256>), SIREN_K(nt_f32_kernel<1, 512>)},
+                                           {SIREN_K(nt_f32_kernel<2, 256>), SIREN_K(nt_f32_kernel<2, 512>)},
+                                           {SIREN_K(nt_f32_kernel<3, 256>), SIREN_K(nt_f32_kernel<3, 512>)}};
+#define SIREN_NT(MODE, TOP, BOT) {SIREN_K(nt_bf16_kernel<MODE, 256, TOP, BOT>), SIREN_K(nt_bf16_kernel<MODE, 512, TOP, BOT>)}
+  static const Kernel<NTArgs> bf16[4][2] = {SIREN_NT(0, false, false), SIREN_NT(1, false, false),
+                                            SIREN_NT(2, false, false), SIREN_NT(3, false, false)};
+  static const Kernel<NTArgs> fused[3][2] = {SIREN_NT(1, false, true), SIREN_NT(1, true, false), SIREN_NT(1, true, true)};
+#undef SIREN_NT
+  const int k = K <= 256 ? 0 : 1;
+  if (prec != kPrecBF16) return f32[mode][k];
+  return top || bot ? fused[2 * top + bot - 1][k] : bf16[mode][k];
+}
+const char* const kNTNames[] = {"nt_gemm fwd", "nt_gemm dx", "nt_gemm first", "nt_gemm dx-input"};
+
+// Which kernel a hidden layer's plain GEMM (MODE_FWD / MODE_DX, nothing folded in) runs on: the
+// tiled kernels above, fp32 on the row-stacked tile (jvp_tan_kernel JT_FWD / JT_DX: 128 rows x all
+// 256 output features per workgroup, 8 waves; nt_f32_kernel's products, K order and epilogues), or
+// the bf16 256x256 input gradient on the ring kernel.
+enum NTForm { NT_TILED, NT_ROWS, NT_RING };
+NTForm nt_form(int prec, int mode, int K, int N) {
+  if (mode != MODE_FWD && mode != MODE_DX) return NT_TILED;
+  if (prec == kPrecF32 && g_f32_rows && K % JNT_KC == 0 && K <= 512 && N <= JADJ_BN) return NT_ROWS;
+  if (prec == kPrecBF16 && mode == MODE_DX && g_dx_ring && K == 256 && N == 256) return NT_RING;
+  return NT_TILED;
+}
+const Kernel<JTanArgs> kRows[2] = {SIREN_K(jvp_tan_kernel<0, 2, 1>), SIREN_K(jvp_tan_kernel<0, 2, 2>)};  // JT_FWD, JT_DX
+dim3 rows_grid(int64_t rows, int64_t nb) { return dim3((unsigned)cdiv(rows, 2 * JADJ_ROWS), (unsigned)nb); }
+int launch_rows(int mode, const NTArgs& a, int64_t nb, int kclass, hipStream_t st) {
+  JTanArgs t;
+  memset(&t, 0, sizeof(t));
+  t.P = mode == MODE_FWD ? a.A : a.Paux;
+  t.U = mode == MODE_DX ? (const float*)a.A : nullptr;
+  t.W = a.W;
+  t.bias = a.bias;
+  t.Uout = (float*)a.C;
+  t.N = a.rows_per_batch;
+  t.Su = 1;
+  t.w_bstride = a.w_bstride;
+  t.b_bstride = a.bias_bstride;
+  t.K = a.K;
+  t.Nout = a.N;
+  t.w0 = a.w0;
+  return launch_kernel(kRows[mode == MODE_FWD ? 0 : 1], rows_grid(a.rows_per_batch, nb), 512, kclass,
+                mode == MODE_FWD ? "f32 rows fwd" : "f32 rows dx", st, t);
 }
 
-template <int PREC, int MODE, bool TOP = false, bool BOT = false>
-int launch_nt(const NTArgs& a, int64_t nb, int kclass, hipStream_t st) {
-  const int kmax = a.K <= 256 ? 256 : 512;
-  if constexpr (PREC == kPrecF32 && (MODE == MODE_FWD || MODE == MODE_DX) && !TOP && !BOT) {
-    // fp32 hidden layers on the row-stacked tile (jvp_tan_kernel JT_FWD / JT_DX: 128 rows x all
-    // 256 output features per workgroup, 8 waves; nt_f32_kernel's products, K order and epilogues)
-    if (g_f32_rows && a.K % JNT_KC == 0 && a.K <= 512 && a.N <= JADJ_BN && a.lda == a.K &&
-        (MODE == MODE_FWD || a.Paux)) {
-      JTanArgs t;
-      memset(&t, 0, sizeof(t));
-      t.P = MODE == MODE_FWD ? a.A : a.Paux;
-      t.U = MODE == MODE_DX ? (const float*)a.A : nullptr;
-      t.W = a.W;
-      t.bias = a.bias;
-      t.Uout = (float*)a.C;
-      t.N = a.rows_per_batch;
-      t.Su = 1;
-      t.w_bstride = a.w_bstride;
-      t.b_bstride = a.bias_bstride;
-      t.K = a.K;
-      t.Nout = a.N;
-      t.w0 = a.w0;
-      const dim3 grid((unsigned)cdiv(a.rows_per_batch, 2 * JADJ_ROWS), (unsigned)nb);
-      tmark_begin(kclass, st);
-      if constexpr (MODE == MODE_FWD) hipLaunchKernelGGL((jvp_tan_kernel<kPrecF32, 2, JT_FWD>), grid, dim3(512), 0, st, t);
-      else hipLaunchKernelGGL((jvp_tan_kernel<kPrecF32, 2, JT_DX>), grid, dim3(512), 0, st, t);
-      tmark_end(kclass, st);
-      return check_launch(MODE == MODE_FWD ? "f32 rows fwd" : "f32 rows dx");
-    }
+// The GEMM of layer l as NTArgs: forward [rows, in] x W_l^T (layer 0: in padded to first_kp), or the
+// input gradient [rows, out] x W_l. A, W, C: the operands as the kernel reads / writes them.
+NTArgs nt_args(const siren_mlp_desc* d, const Geo& g, int l, bool fwd, const void* A, const void* W, void* C) {
+  NTArgs a;
+  memset(&a, 0, sizeof(a));
+  const int in = fwd && l == 0 ? first_kp(d) : d->dims[l], out = d->dims[l + 1];
+  a.A = A;
+  a.W = W;
+  a.C = C;
+  a.rows_per_batch = g.rows;
+  a.w_bstride = bstride(d, (int64_t)out * in);
+  a.K = fwd ? in : out;
+  a.N = fwd ? out : in;
+  a.lda = fwd ? d->dims[l] : out;
+  a.w0 = d->w0;
+  if (fwd) {
+    a.bias = d->bias[l];
+    a.bias_bstride = bstride(d, out);
   }
-  if constexpr (PREC == kPrecBF16 && MODE == MODE_DX && !TOP && !BOT) {
-    if (g_dx_ring && a.K == 256 && a.N == 256) {
-      tmark_begin(SIREN_KCLASS_DX_RING, st);
-      hipLaunchKernelGGL((dx_ring_bf16_kernel<0, false>), ring_grid(a, nb), dim3(512), 0, st, a);
-      tmark_end(SIREN_KCLASS_DX_RING, st);
-      return check_launch("dx_ring");
-    }
-  }
-  const dim3 grid = nt_grid(a, nb, PREC);
-  tmark_begin(kclass, st);
-  if constexpr (PREC == kPrecBF16) {
-    if (kmax == 256) hipLaunchKernelGGL((nt_bf16_kernel<MODE, 256, TOP, BOT>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((nt_bf16_kernel<MODE, 512, TOP, BOT>), grid, dim3(512), 0, st, a);
-  } else {
-    static_assert(PREC == kPrecBF16 || !(TOP || BOT), "backward fusions are bf16-mode paths");
-    if (kmax == 256) hipLaunchKernelGGL((nt_f32_kernel<MODE>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((nt_f32_kernel<MODE, 512>), grid, dim3(512), 0, st, a);
-  }
-  tmark_end(kclass, st);
-  static const char* const names[] = {"nt_gemm fwd", "nt_gemm dx", "nt_gemm first", "nt_gemm dx-input"};
-  return check_launch(names[MODE]);
+  return a;
 }
+
+// The weight gradient of layer l as TNArgs: D = dZ_l, P = the layer's input, one slab per split.
+TNArgs tn_args(const siren_mlp_desc* d, const Geo& g, int l, const void* D, const void* P, float* part,
+               int64_t rows_per_split) {
+  TNArgs a;
+  memset(&a, 0, sizeof(a));
+  a.D = D;
+  a.P = P;
+  a.part = part;
+  a.rows_per_batch = g.rows;
+  a.rows_per_split = rows_per_split;
+  a.M = d->dims[l + 1];
+  a.N = d->dims[l];
+  a.split_stride = split_stride(g, (int64_t)a.M * a.N + a.M);
+  a.w0 = d->w0;
+  return a;
+}
+
 
 // Register-resident forward (siren_fwdreg.hip): one weight-prep launch, one forward launch.
 int fused_forward_reg(const siren_mlp_desc* d, const Geo& g, const Layout& lo, const float* x, float* y,
@@ -500,19 +468,7 @@ int fused_forward_reg(const siren_mlp_desc* d, const Geo& g, const Layout& lo, c
   a.w0 = d->w0;
   a.ffB = d->ff_B;
   a.ffin = d->ff_B ? d->ff_in : 0;
-  if (L) {
-    a.ltgt = L->target;
-    a.lk0 = L->k0;
-    a.lmask = L->mask;
-    a.lhf = L->hf;
-    a.ldc = L->y_dc;
-    a.ldy = L->dy;
-    a.lloss = L->loss;
-    a.lpart = (float*)L->loss_workspace;
-    a.lcounter = (unsigned*)((char*)L->loss_workspace + SSE_MAX_BLOCKS * 4);
-    a.lnoise = L->noise;
-    a.lweight = L->weight;
-  }
+  if (L) set_loss(a, *L);
   const int64_t tiles = cdiv(g.rows, FREG_WG_ROWS);
   const int64_t per = std::max<int64_t>(1, 256 / g.nb);
   dim3 grid((unsigned)std::min<int64_t>(tiles, per), (unsigned)g.nb);
@@ -626,519 +582,547 @@ int forward_impl(const siren_mlp_desc* d, const float* x, float* y, char* saved,
   };
   // Layer 0: MFMA GEMM for wide inputs, VALU otherwise.
   if (wide_input(d)) {
-    NTArgs a;
-    a.A = x;
-    a.W = wbuf + lo.w_op_off[0];
-    a.bias = d->bias[0];
-    a.Paux = nullptr;
-    a.C = phase_buf(0);
-    a.rows_per_batch = g.rows;
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[1] * first_kp(d) : 0;
-    a.bias_bstride = d->weights_batched ? d->dims[1] : 0;
-    a.K = first_kp(d);
-    a.N = d->dims[1];
-    a.lda = d->dims[0];
+    NTArgs a = nt_args(d, g, 0, true, x, wbuf + lo.w_op_off[0], phase_buf(0));
     a.a_vec = (d->dims[0] % 4 == 0) && aligned16(x);
-    a.w0 = d->w0;
-    if ((rc = launch_nt<PREC, MODE_FIRST>(a, g.nb, 0, st))) return rc;
+    if ((rc = launch_kernel(nt_kernel(PREC, MODE_FIRST, a.K), nt_grid(g.rows, a.K, a.N, g.nb, PREC), 512, 0,
+                     kNTNames[MODE_FIRST], st, a)))
+      return rc;
   } else {
+    static const Kernel<FirstFwdArgs> k[2][2] = {{SIREN_K(first_fwd_kernel<0, 4>), SIREN_K(first_fwd_kernel<0, 16>)},
+                                                 {SIREN_K(first_fwd_kernel<1, 4>), SIREN_K(first_fwd_kernel<1, 16>)}};
     FirstFwdArgs a;
     a.x = x;
     a.W = d->weight[0];
     a.b = d->bias[0];
     a.P = phase_buf(0);
     a.rows_per_batch = g.rows;
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[1] * d->dims[0] : 0;
-    a.b_bstride = d->weights_batched ? d->dims[1] : 0;
+    a.w_bstride = bstride(d, (int64_t)d->dims[1] * d->dims[0]);
+    a.b_bstride = bstride(d, d->dims[1]);
     a.C = d->dims[0];
     a.F = d->dims[1];
     a.w0 = d->w0;
     const unsigned gx = grid1d(g.rows * (a.F / 8), std::max<int64_t>(1, 4096 / g.nb));
-    if (a.C <= 4)
-      hipLaunchKernelGGL((first_fwd_kernel<PREC, 4>), dim3(gx, (unsigned)g.nb), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((first_fwd_kernel<PREC, 16>), dim3(gx, (unsigned)g.nb), dim3(256), 0, st, a);
-    if ((rc = check_launch("first_fwd"))) return rc;
+    if ((rc = launch_kernel(k[PREC][a.C <= 4 ? 0 : 1], dim3(gx, (unsigned)g.nb), 256, 0, "first_fwd", st, a))) return rc;
   }
   // Hidden MFMA layers.
   for (int l = 1; l + 1 < g.L; ++l) {
-    NTArgs a;
-    a.A = phase_buf(l - 1);
-    a.W = PREC == kPrecBF16 ? (const void*)(wbuf + lo.w_op_off[l]) : (const void*)d->weight[l];
-    a.bias = d->bias[l];
-    a.Paux = nullptr;
-    a.C = phase_buf(l);
-    a.rows_per_batch = g.rows;
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[l + 1] * d->dims[l] : 0;
-    a.bias_bstride = d->weights_batched ? d->dims[l + 1] : 0;
-    a.K = d->dims[l];
-    a.N = d->dims[l + 1];
-    a.lda = a.K;
-    a.a_vec = 0;
-    a.w0 = d->w0;
-    if ((rc = launch_nt<PREC, MODE_FWD>(a, g.nb, SIREN_KCLASS_FWD_GEMM, st))) return rc;
+    const NTArgs a = nt_args(d, g, l, true, phase_buf(l - 1),
+                             PREC == kPrecBF16 ? (const void*)(wbuf + lo.w_op_off[l]) : (const void*)d->weight[l],
+                             phase_buf(l));
+    if (nt_form(PREC, MODE_FWD, a.K, a.N) == NT_ROWS)
+      rc = launch_rows(MODE_FWD, a, g.nb, SIREN_KCLASS_FWD_GEMM, st);
+    else
+      rc = launch_kernel(nt_kernel(PREC, MODE_FWD, a.K), nt_grid(g.rows, a.K, a.N, g.nb, PREC), 512,
+                  SIREN_KCLASS_FWD_GEMM, kNTNames[MODE_FWD], st, a);
+    if (rc) return rc;
   }
   // Output layer (VALU).
-  {
-    const int l = g.L - 1;
-    LastFwdArgs a;
-    a.P = phase_buf(l - 1);
-    a.W = d->weight[l];
-    a.b = d->bias[l];
-    a.y = y;
-    a.rows_per_batch = g.rows;
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[l + 1] * d->dims[l] : 0;
-    a.b_bstride = d->weights_batched ? d->dims[l + 1] : 0;
-    a.F = d->dims[l];
-    a.O = d->dims[l + 1];
-    a.sine_out = d->outermost_linear ? 0 : 1;
-    a.w0 = d->w0;
-    a.ltgt = a.lk0 = a.lmask = a.lhf = nullptr;
-    a.ldc = a.ldy = a.lloss = a.lpart = nullptr;
-    a.lcounter = nullptr;
-    a.lnoise = a.lweight = 0.f;
-    if (L) {
-      a.ltgt = L->target;
-      a.lk0 = L->k0;
-      a.lmask = L->mask;
-      a.lhf = L->hf;
-      a.ldc = L->y_dc;
-      a.ldy = L->dy;
-      a.lloss = L->loss;
-      a.lpart = (float*)L->loss_workspace;
-      a.lcounter = (unsigned*)((char*)L->loss_workspace + SSE_MAX_BLOCKS * 4);
-      a.lnoise = L->noise;
-      a.lweight = L->weight;
-    }
-    if ((rc = dispatch_last_fwd<PREC>(a, g.nb, st))) return rc;
-  }
-  return SIREN_OK;
-}
-
-// One pair_ring_bf16_kernel launch for hidden layer l (kind: see backward_impl) and the
-// reductions of its partial slabs.
-template <int PREC>
-int launch_pair(const siren_mlp_desc* d, const Geo& g, const Layout& lo, int kind, int l, const float* x,
-                const TopArgs& ta, char* ws, const char* saved, float* part, float* const* dW, float* const* db,
-                float* dx, int cur, ReduceList& pend, hipStream_t st) {
-  const int M = d->dims[l + 1], N = d->dims[l], C = d->dims[0], F0 = d->dims[1], O = d->dims[g.L];
-  const int64_t npair = pair_count(g);
-  TNArgs w;
-  memset(&w, 0, sizeof(w));
-  w.D = ws + lo.dz_off[cur];
-  w.P = kind == 3 ? (const void*)x : (const void*)(saved + lo.saved_off[l - 1]);
-  w.part = part;
-  w.rows_per_batch = g.rows;
-  w.rows_per_split = 0;  // ranges come from the pair index
-  w.split_stride = split_stride(g, (int64_t)M * N + M);
-  w.M = M;
-  w.N = N;
-  w.w0 = d->w0;
-  w.top = ta;
-  w.pair_roles = g_pair_roles;
-  w.prof = g_ring_prof ? g_ring_prof + (int64_t)(g_ring_prof_n++) * 256 * 8 * RING_NPROF : nullptr;
-  NTArgs a;
+  const int l = g.L - 1;
+  LastFwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.A = ws + lo.dz_off[cur];
-  a.W = saved + lo.wt_op_off[l];
-  a.Paux = kind == 3 ? nullptr : (const void*)(saved + lo.saved_off[l - 1]);
-  a.C = ws + lo.dz_off[cur ^ 1];
+  a.P = phase_buf(l - 1);
+  a.W = d->weight[l];
+  a.b = d->bias[l];
+  a.y = y;
   a.rows_per_batch = g.rows;
-  a.w_bstride = d->weights_batched ? (int64_t)M * N : 0;
-  a.K = M;
-  a.N = N;
-  a.lda = M;
+  a.w_bstride = bstride(d, (int64_t)d->dims[l + 1] * d->dims[l]);
+  a.b_bstride = bstride(d, d->dims[l + 1]);
+  a.F = d->dims[l];
+  a.O = d->dims[l + 1];
+  a.sine_out = d->outermost_linear ? 0 : 1;
   a.w0 = d->w0;
-  a.top = ta;
-  a.prof = w.prof;
-  a.stagger = g_dx_stagger ? 1 : 0;
-  const int64_t bot_stride = split_stride(g, (int64_t)F0 * C + F0);
-  if (kind == 3) {
-    w.rec_W0 = d->weight[0];
-    w.rec_w0_bstride = d->weights_batched ? (int64_t)F0 * C : 0;
-    w.rec_b0 = d->bias[0];
-    w.rec_b0_bstride = d->weights_batched ? F0 : 0;
-    a.C = dx;
-    a.bot.x = x;
-    a.bot.W0 = d->weight[0];
-    a.bot.w0_bstride = w.rec_w0_bstride;
-    a.bot.b0 = d->bias[0];
-    a.bot.b0_bstride = w.rec_b0_bstride;
-    a.bot.part = (float*)(ws + lo.partB_off);
-    a.bot.split_stride = bot_stride;
-    a.bot.C = C;
-  }
-  const int64_t nx = npair, nw = npair;  // input-gradient / weight-gradient workgroups (slabs)
-  const dim3 grid((unsigned)(2 * npair), (unsigned)g.nb);
-  const int kcls = kind == 1 ? SIREN_KCLASS_PAIR_RING : kind == 2 ? SIREN_KCLASS_PAIR_RING_TOP : SIREN_KCLASS_PAIR_RING_BOT;
-  tmark_begin(kcls, st);
-  const ReduceMultiArgs prev = pend.a;  // the previous pair launch's slabs, reduced in this one's tail
-  if (kind == 1) {
-    hipLaunchKernelGGL((pair_ring_bf16_kernel<0, false, false, 0, 0>), grid, dim3(512), 0, st, a, w, prev);
-  } else if (kind == 2) {
-    if (O == 1) hipLaunchKernelGGL((pair_ring_bf16_kernel<0, false, false, 1, 0>), grid, dim3(512), 0, st, a, w, prev);
-    else hipLaunchKernelGGL((pair_ring_bf16_kernel<0, false, false, 2, 0>), grid, dim3(512), 0, st, a, w, prev);
-  } else {
-#define SIREN_PAIR_BOT(CC)                                                                                         \
-  if (dx) hipLaunchKernelGGL((pair_ring_bf16_kernel<CC, true, true, 0, CC>), grid, dim3(512), 0, st, a, w, prev);   \
-  else hipLaunchKernelGGL((pair_ring_bf16_kernel<CC, false, true, 0, CC>), grid, dim3(512), 0, st, a, w, prev);
-    switch (C) {
-      case 1: SIREN_PAIR_BOT(1) break;
-      case 2: SIREN_PAIR_BOT(2) break;
-      case 3: SIREN_PAIR_BOT(3) break;
-      default: SIREN_PAIR_BOT(4) break;
-    }
-#undef SIREN_PAIR_BOT
-  }
-  tmark_end(kcls, st);
-  int rc = check_launch("pair_ring");
-  if (rc) return rc;
-  // this launch's slabs: reduced by the next pair launch, or by a reduce_multi launch (flush)
-  ReduceList red;
-  red.add(part, nw, w.split_stride, g.nb, (int64_t)M * N + M, (int64_t)M * N, dW[l], db[l]);
-  if (kind == 2) red.add(ta.partL, nw, ta.partL_stride, g.nb, (int64_t)O * M + O, (int64_t)O * M, dW[g.L - 1], db[g.L - 1]);
-  if (kind == 3) red.add(a.bot.part, nx, bot_stride, g.nb, (int64_t)F0 * C + F0, (int64_t)F0 * C, dW[0], db[0]);
-  pend = red;
-  return SIREN_OK;
+  if (L) set_loss(a, *L);
+  return launch_last_fwd(PREC, a, g.nb, st);
 }
 
-template <int PREC>
-int backward_impl(const siren_mlp_desc* d, const float* x, const float* dy, const char* saved,
-                  char* ws, float* const* dW, float* const* db, float* dx, hipStream_t st,
-                  const float* dy_scale = nullptr) {
-  const Geo g = geo_of(d);
-  const Layout lo = layout_of(d);
-  int rc = SIREN_OK;
-  float* part = (float*)(ws + lo.part_off);
-  auto P = [&](int l) -> const void* { return saved + lo.saved_off[l]; };
-  const int O = d->dims[g.L], C = d->dims[0], F0 = d->dims[1];
-  // slab reduction of the last pair launch, not yet issued (see launch_pair)
-  ReduceList pend;
-  int npair_launches = 0;
-  auto flush = [&]() -> int {
-    const int r = pend.launch(st);
-    pend = ReduceList();
-    return r;
-  };
+// The backward pass as data: plan_backward decides every launch from the descriptor, the options
+// and the alignment of x and dy; backward_impl walks the plan; siren_mlp_backward_plan prints it.
+enum OutForm { OUT_LAST_BWD, OUT_TILED, OUT_RING };  // output layer: its own kernel, or folded into the top layer's
+// first layer: folded into layer 1's ring / tiled kernels, wide MFMA (tn_dw RAW + MODE_DXLIN), or the VALU kernels
+enum FirstForm { FIRST_RING, FIRST_TILED, FIRST_MFMA, FIRST_VALU };
+enum Slab { SLAB_NONE, SLAB_PART, SLAB_PART2, SLAB_PARTL, SLAB_PARTB };  // Layout part / part2 / partL / partB
+// where a launch's partial slabs are summed: a reduce launch right after it, the tail of the next
+// pair launch, or a reduce_multi launch further down
+enum Reduce { RED_NONE, RED_OWN, RED_NEXT_PAIR, RED_FLUSH };
+enum Kern {
+  K_XCOPY,         // x copied to a 16-byte aligned buffer (the ring kernels DMA it in 16-byte pieces)
+  K_LAST_BWD,      // output layer on its own kernel
+  K_REDUCE,        // the slabs out[0] summed into dW / db of their layer
+  K_REDUCE_MULTI,  // the slabs of pair launch `src` summed in one launch
+  K_PAIR,          // both gradients of a 256x256 layer on co-scheduled workgroup pairs (pair_ring_bf16_kernel): a
+                   //   middle layer, the top layer with the output layer (top), layer 1 with the first layer (bot, rec)
+  K_DW_TILED,      // weight gradient: 128x128-tile split-K kernel (top: output layer folded in; layer 0: raw x)
+  K_DW_RING,       //   ring kernel: middle layer, top layer (top), layer 1 rebuilding P_0 from x (rec)
+  K_DW_ROWS,       //   fp32 all-rows tile (jvp_tn2_kernel)
+  K_DX_TILED,      // input gradient: tiled kernel (top / bot: output / first layer folded in; layer 0: MODE_DXLIN)
+  K_DX_RING,       //   ring kernel: middle layer, top layer (top), layer 1 with the first layer (bot)
+  K_DX_ROWS,       //   fp32 row-stacked tile (jvp_tan_kernel JT_DX)
+  K_FIRST          // first layer on the VALU kernels (dx_out: the launch also, or only, writes dx)
+};
+using PairKernel = Kernel<NTArgs, TNArgs, ReduceMultiArgs>;
+struct SlabUse {
+  Slab buf;
+  int layer;  // whose dW / db the slabs are partial sums of
+  int64_t nsplit;
+};
+struct Launch {
+  Kern kern;
+  const void* fn;    // Kernel<Args>::fn of the Args the kind takes, and its profiler name
+  const char* sym;
+  const char* what;  // its name in a launch error
+  int kclass, layer;
+  int cur;           // which dZ buffer holds the layer's dZ (the other receives the input gradient)
+  dim3 grid;
+  unsigned block;
+  bool top, bot, rec, dx_out;  // output / first layer folded in, P_0 rebuilt from x, writes dx (not dZ_{l-1})
+  bool p_vec;        // layer-0 K_DW_TILED: x rows are read as 16-byte vectors (C % 4 == 0, aligned x)
+  int64_t rows_per_split;
+  SlabUse out[2];    // slabs written (K_REDUCE: read)
+  Reduce reduce;
+  int src = -1;      // K_REDUCE_MULTI: the pair launch it reduces; K_PAIR: the one its tail reduces (-1: none)
+};
+struct BwdPlan {
+  const char* error = nullptr;  // a shape the kernels do not cover (SIREN_EINVAL)
+  bool copy_x = false;
+  OutForm out = OUT_LAST_BWD;
+  FirstForm first = FIRST_VALU;
+  int pair_roles = 3, stagger = 0;  // debug_pair_roles / dx_stagger, passed to the ring kernels
+  int n = 0, npair = 0;  // launches; pair launches among them
+  int cur = 0;  // (while planning) dZ ping-pong index holding dZ of the current layer
+  Launch steps[6 * SIREN_MAX_LAYERS];  // (at most 5 per hidden layer and 7 around them)
+
+  template <class K>
+  Launch& add(Kern kern, const K& k, const char* what, int kclass, int layer, dim3 grid, unsigned block) {
+    assert(n < (int)(sizeof(steps) / sizeof(steps[0])));
+    return steps[n++] = Launch{kern, (const void*)k.fn, k.sym, what, kclass, layer, cur, grid, block};
+  }
+};
+
+// dW_l then db_l: one partial slab
+inline int64_t slab_elems(const siren_mlp_desc* d, int l) { return (int64_t)d->dims[l + 1] * d->dims[l] + d->dims[l + 1]; }
+
+BwdPlan plan_backward(const siren_mlp_desc* d, const Geo& g, const Layout& lo, bool want_dx, bool x_aligned16,
+                      bool dy_aligned16) {
+  static const Kernel<int> kCopy = {nullptr, "hipMemcpyAsync"}, kReduce = {nullptr, "siren::reduce_kernel"};  // (not via fn)
+  static const Kernel<ReduceMultiArgs> kReduceMulti = SIREN_K(reduce_multi_kernel);
+  BwdPlan p;
+  const int prec = g.prec, L = g.L, O = d->dims[L], C = d->dims[0], F0 = d->dims[1];
+  const int c4 = std::min(C, 4) - 1, topo = O == 1 ? 1 : 2;  // table indices of the first- / output-layer fusions
+  const bool bf16 = prec == kPrecBF16;
+  const unsigned nb = (unsigned)g.nb;
+  p.pair_roles = g_pair_roles;
+  p.stagger = g_dx_stagger ? 1 : 0;
   // bf16-mode fusions (siren_gemm.hip TopArgs / BotArgs): the output layer's backward folds into
   // the top hidden layer's kernels, the first layer's weight gradient into the bottom one's.
-  const bool fuse = PREC == kPrecBF16 && g_fused_backward && g.L >= 3;
+  const bool fuse = bf16 && g_fused_backward && L >= 3;
   // P_0 not kept (p0_recompute): layer 1 runs on the ring kernels that rebuild it from x, whatever
   // the options say; they DMA x in 16-byte pieces, so a misaligned x is copied first.
   const bool rec = lo.p0_rec;
-  if (rec && !aligned16(x)) {
-    if (hipMemcpyAsync(ws + lo.xcopy_off, x, g.total * C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return fail(SIREN_ELAUNCH, "x copy: %s", hipGetErrorString(hipGetLastError()));
-    x = (const float*)(ws + lo.xcopy_off);
-  }
+  p.copy_x = rec && !x_aligned16;
+  if (p.copy_x) p.add(K_XCOPY, kCopy, "x copy", 0, 0, dim3(0, 0, 0), 0);
+  const bool x16 = x_aligned16 || p.copy_x;
   const bool top_ok = fuse && d->outermost_linear && O <= TOP_MAXO && (g.rows * O) % 4 == 0 && g.rows * O >= 4 &&
-                      aligned16(dy) && !(rec && g.L == 3);
+                      dy_aligned16 && !(rec && L == 3);
   // output layer folded into the top layer's ring kernels (256x256 top layer below another layer)
-  const bool ring_top = top_ok && g_ring_top && g.L >= 4 && d->dims[g.L - 1] == 256 && d->dims[g.L - 2] == 256;
-  const bool top = ring_top || (top_ok && g_fuse_top && d->dims[g.L - 1] <= 256);
-  // first-layer fusion: the ring kernel (256x256 bottom layer) also produces dx; the older
-  // kernel only without dx
-  const bool ring_bot = rec || (fuse && g_dx_ring && !wide_input(d) && C <= BOT_MAXC && F0 == 256 &&
-                                d->dims[2] == 256 && !(top && g.L == 3) && (g.rows * C) % 4 == 0 &&
-                                g.rows * C >= 4 && aligned16(x));
-  const bool bot = ring_bot || (fuse && !dx && !wide_input(d) && C <= BOT_MAXC && F0 <= 256 &&
-                                (g.rows * C) % 4 == 0 && g.rows * C >= 4 && aligned16(x) &&
-                                !(top && g.L == 3));  // one hidden layer: the output-layer fusion only
-  int cur = 0;  // dz ping-pong index holding dZ of the current layer
-  // Output layer: dZ_{L-2}, dW_{L-1}, db_{L-1}.
-  if (!top) {
-    const int l = g.L - 1;
-    const Split s = valu_split(g);
-    LastBwdArgs a;
-    a.P = P(l - 1);
-    a.W = d->weight[l];
-    a.b = d->bias[l];
-    a.dy = dy;
-    a.dy_scale = dy_scale;
-    a.dZ = ws + lo.dz_off[cur];
-    a.part = part;
-    a.rows_per_batch = g.rows;
+  const bool ring_top = top_ok && g_ring_top && L >= 4 && d->dims[L - 1] == 256 && d->dims[L - 2] == 256;
+  const bool top = ring_top || (top_ok && g_fuse_top && d->dims[L - 1] <= 256);
+  // first-layer fusion: the ring kernel (256x256 bottom layer) also produces dx; the tiled kernel
+  // only without dx. One hidden layer: the output-layer fusion only.
+  const bool bot_ok = fuse && !wide_input(d) && C <= BOT_MAXC && (g.rows * C) % 4 == 0 && g.rows * C >= 4 && x16 &&
+                      !(top && L == 3);
+  const bool ring_bot = rec || (bot_ok && g_dx_ring && F0 == 256 && d->dims[2] == 256);
+  const bool bot = ring_bot || (bot_ok && !want_dx && F0 <= 256);
+  p.out = ring_top ? OUT_RING : top ? OUT_TILED : OUT_LAST_BWD;
+  p.first = ring_bot ? FIRST_RING : bot ? FIRST_TILED : wide_input(d) ? FIRST_MFMA : FIRST_VALU;
+
+  // a launch that writes s.nsplit slabs of dW / db[layer] to `part`, and the reduce launch that sums them
+  auto writes = [&](Launch& a, int layer, const Split& s) {
     a.rows_per_split = s.rows_per_split;
-    a.F = d->dims[l];
-    a.O = d->dims[l + 1];
-    a.split_stride = split_stride(g, (int64_t)a.O * a.F + a.O);
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[l + 1] * d->dims[l] : 0;
-    a.b_bstride = d->weights_batched ? d->dims[l + 1] : 0;
-    a.sine_out = d->outermost_linear ? 0 : 1;
-    a.w0 = d->w0;
-    if ((rc = dispatch_last_bwd<PREC>(a, s.nsplit, g.nb, st))) return rc;
-    if ((rc = launch_reduce(part, s.nsplit, a.split_stride, g.nb, (int64_t)a.O * a.F + a.O,
-                            (int64_t)a.O * a.F, dW[l], db[l], st)))
-      return rc;
-  }
-  TopArgs ta;
-  memset(&ta, 0, sizeof(ta));
-  if (top) {
-    const int FL = d->dims[g.L - 1];
-    ta.Ptop = P(g.L - 2);
-    ta.dy = dy;
-    ta.dy_scale = dy_scale;
-    ta.WL = d->weight[g.L - 1];
-    ta.wl_bstride = d->weights_batched ? (int64_t)O * FL : 0;
-    ta.partL = (float*)(ws + lo.partL_off);
-    ta.partL_stride = split_stride(g, (int64_t)O * FL + O);
-    ta.O = O;
+    a.out[0] = {SLAB_PART, layer, s.nsplit};
+    a.reduce = RED_OWN;
+  };
+  auto reduce_of = [&](int layer, Slab buf, int64_t nsplit) {
+    p.add(K_REDUCE, kReduce, "reduce", 0, layer, dim3((unsigned)reduce_blocks(g.nb, slab_elems(d, layer))), 256).out[0] = {
+        buf, layer, nsplit};
+  };
+  int pend = -1;  // the pair launch whose slabs are not reduced yet
+  auto reduce_pending = [&] {
+    if (pend < 0) return;
+    int64_t blocks = 0;
+    for (const SlabUse& u : p.steps[pend].out)
+      if (u.buf != SLAB_NONE) blocks += reduce_blocks(g.nb, slab_elems(d, u.layer));
+    p.steps[pend].reduce = RED_FLUSH;
+    p.add(K_REDUCE_MULTI, kReduceMulti, "reduce_multi", 0, p.steps[pend].layer, dim3((unsigned)blocks), 256).src = pend;
+    pend = -1;
+  };
+
+  if (!top) {  // output layer: dZ_{L-2}, dW_{L-1}, db_{L-1}
+    static const Kernel<LastBwdArgs> k[2][2][3] = {{SIREN_IT(last_bwd_kernel, 0, 2), SIREN_IT(last_bwd_kernel, 0, 8)},
+                                                   {SIREN_IT(last_bwd_kernel, 1, 2), SIREN_IT(last_bwd_kernel, 1, 8)}};
+    const Split s = valu_split(g);
+    writes(p.add(K_LAST_BWD, k[prec][O <= 2 ? 0 : 1][it_index(d->dims[L - 1])], "last_bwd", 0, L - 1,
+                 dim3((unsigned)s.nsplit, nb), 256),
+           L - 1, s);
+    reduce_of(L - 1, SLAB_PART, s.nsplit);
   }
   // Hidden MFMA layers, top to bottom.
-  for (int l = g.L - 2; l >= 1; --l) {
+  for (int l = L - 2; l >= 1; --l) {
     const int M = d->dims[l + 1], N = d->dims[l];
-    const bool is_top = top && l == g.L - 2;
-    const bool is_bot = bot && l == 1;
-    const bool rec1 = rec && l == 1;
-    const bool ring_t = ring_top && l == g.L - 2;
-    if (PREC == kPrecBF16 && g_bwd_ring && !is_top && !is_bot && !rec1 && M == 256 && N == 256) {
-      // both gradients of a middle layer in one pass (bwd_ring_bf16_kernel)
-      const Split s = dw_ring_split(g);
-      BwdArgs b;
-      memset(&b, 0, sizeof(b));
-      b.dZ = (const bf16*)(ws + lo.dz_off[cur]);
-      b.P = (const uint16_t*)P(l - 1);
-      b.Wt = (const bf16*)(saved + lo.wt_op_off[l]);
-      b.dZo = (bf16*)(ws + lo.dz_off[cur ^ 1]);
-      b.part = part;
-      b.rows_per_batch = g.rows;
-      b.rows_per_split = s.rows_per_split;
-      b.split_stride = split_stride(g, (int64_t)M * N + M);
-      b.w_bstride = d->weights_batched ? (int64_t)M * N : 0;
-      b.w0 = d->w0;
-      if ((rc = flush())) return rc;
-      tmark_begin(SIREN_KCLASS_BWD_FUSED, st);
-      hipLaunchKernelGGL(bwd_ring_bf16_kernel, dim3((unsigned)s.nsplit, (unsigned)g.nb), dim3(256), 0, st, b);
-      tmark_end(SIREN_KCLASS_BWD_FUSED, st);
-      if ((rc = check_launch("bwd_ring"))) return rc;
-      if ((rc = launch_reduce(part, s.nsplit, b.split_stride, g.nb, (int64_t)M * N + M, (int64_t)M * N, dW[l],
-                              db[l], st)))
-        return rc;
-      cur ^= 1;
-      continue;
+    const bool is_top = top && l == L - 2, is_bot = bot && l == 1, rec1 = rec && l == 1, ring_t = ring_top && l == L - 2;
+    const bool sq256 = bf16 && M == 256 && N == 256;
+    if (sq256 && g_pair_ring && pair_ok(g) &&
+        ((rec1 && !is_top) || (ring_t && !is_bot) || (!is_top && !is_bot && !rec1 && g_dw_ring && g_dx_ring))) {
+      static const PairKernel mid[3] = {SIREN_K(pair_ring_bf16_kernel<0, false, false, 0, 0>),
+                                        SIREN_K(pair_ring_bf16_kernel<0, false, false, 1, 0>),
+                                        SIREN_K(pair_ring_bf16_kernel<0, false, false, 2, 0>)};
+#define SIREN_PAIR_BOT(CC, DX) SIREN_K(pair_ring_bf16_kernel<CC, DX, true, 0, CC>)
+      static const PairKernel low[2][4] = {SIREN_C4(SIREN_PAIR_BOT, false), SIREN_C4(SIREN_PAIR_BOT, true)};
+#undef SIREN_PAIR_BOT
+      // consecutive pair launches alternate slab buffers (the pending reduction reads the other
+      // one); without a second buffer, or without the tail reduction, the pending one goes first
+      if (!g_tail_reduce || lo.part2_off < 0) reduce_pending();
+      const int64_t np = pair_count(g);
+      const bool pb = rec1 && !is_top, pt = !pb && ring_t;
+      Launch& s = p.add(K_PAIR, pb ? low[want_dx ? 1 : 0][c4] : mid[pt ? topo : 0], "pair_ring",
+                        pb ? SIREN_KCLASS_PAIR_RING_BOT : pt ? SIREN_KCLASS_PAIR_RING_TOP : SIREN_KCLASS_PAIR_RING, l,
+                        dim3((unsigned)(2 * np), nb), 512);
+      s.top = pt;
+      s.bot = s.rec = s.dx_out = pb;
+      s.out[0] = {lo.part2_off >= 0 && (p.npair & 1) ? SLAB_PART2 : SLAB_PART, l, np};
+      if (pt) s.out[1] = {SLAB_PARTL, L - 1, np};
+      if (pb) s.out[1] = {SLAB_PARTB, 0, np};
+      s.src = pend;
+      if (pend >= 0) p.steps[pend].reduce = RED_NEXT_PAIR;
+      pend = p.n - 1;
+      ++p.npair;
+      p.cur ^= 1;
+      if (!pb) continue;
+      reduce_pending();  // first layer done
+      return p;
     }
-    if (PREC == kPrecBF16 && g_pair_ring && pair_ok(g) && M == 256 && N == 256) {
-      // both gradients in one launch on co-scheduled workgroup pairs (pair_ring_bf16_kernel):
-      // 1 = middle layer, 2 = top layer with the output layer folded in, 3 = bottom layer with the
-      // first layer folded in and P_0 rebuilt from x
-      const int kind = (rec1 && !is_top)                                   ? 3
-                       : (ring_t && !is_bot)                               ? 2
-                       : (!is_top && !is_bot && !rec1 && g_dw_ring && g_dx_ring) ? 1
-                                                                           : 0;
-      if (kind) {
-        // consecutive pair launches alternate slab buffers (the pending reduction reads the other
-        // one); without a second buffer the pending reduction goes first
-        float* pp = part;
-        if (!g_tail_reduce && (rc = flush())) return rc;
-        if (lo.part2_off >= 0) {
-          if (npair_launches++ & 1) pp = (float*)(ws + lo.part2_off);
-        } else if ((rc = flush())) {
-          return rc;
-        }
-        if ((rc = launch_pair<PREC>(d, g, lo, kind, l, x, ta, ws, saved, pp, dW, db, dx, cur, pend, st))) return rc;
-        if (kind == 3) return flush();  // first layer done
-        cur ^= 1;
-        continue;
-      }
+    reduce_pending();  // the per-layer kernels below reuse `part`
+    {                  // weight gradient
+      static const Kernel<TNArgs> tiled[2][2] = {{SIREN_K(tn_dw_kernel<0, false, false>), {nullptr, nullptr}},
+                                                 {SIREN_K(tn_dw_kernel<1, false, false>), SIREN_K(tn_dw_kernel<1, false, true>)}};
+      static const Kernel<TNArgs> mid[3] = {SIREN_K(dw_ring_bf16_kernel<0, 0>), SIREN_K(dw_ring_bf16_kernel<0, 1>),
+                                            SIREN_K(dw_ring_bf16_kernel<0, 2>)};
+#define SIREN_DW_REC(CC, Z) SIREN_K(dw_ring_bf16_kernel<CC, Z>)
+      static const Kernel<TNArgs> recs[4] = SIREN_C4(SIREN_DW_REC, 0);
+#undef SIREN_DW_REC
+      static const Kernel<JTNArgs> rows_k = SIREN_K(jvp_tn2_kernel<false>);
+      const bool ring = rec1 || ring_t || (sq256 && g_dw_ring && !is_top);
+      // fp32: jvp_tn2_kernel over the primal stream alone (S = 1: X = sin(P_{l-1}), D = dZ_l):
+      // all 256 dW rows per workgroup, so each X element is formed once per launch
+      const bool rows = !bf16 && g_f32_rows && jvp_tn2_ok(M, N);
+      const Split s = ring ? dw_ring_split(g) : rows ? jtn2_split(g, g.rows, N) : tn_split(g, M, N);
+      const unsigned ns = (unsigned)s.nsplit;
+      Launch& a =
+          ring   ? p.add(K_DW_RING, rec1 ? recs[c4] : mid[ring_t ? topo : 0], "tn_dw",
+                         rec1 ? SIREN_KCLASS_DW_RING_REC : ring_t ? SIREN_KCLASS_DW_RING_TOP : SIREN_KCLASS_DW_RING, l,
+                         dim3(ns, nb), 512)
+          : rows ? p.add(K_DW_ROWS, rows_k, "tn_dw", SIREN_KCLASS_DW_GEMM, l, dim3((unsigned)cdiv(N, JTN2_BN), ns, nb), 512)
+                 : p.add(K_DW_TILED, tiled[prec][is_top ? 1 : 0], "tn_dw", SIREN_KCLASS_DW_GEMM, l,
+                         dim3((unsigned)(cdiv(M, TN_BM) * cdiv(N, TN_BN)), ns, nb), 256);
+      writes(a, l, s);
+      a.top = is_top;
+      a.rec = rec1;
+      if (is_top) a.out[1] = {SLAB_PARTL, L - 1, s.nsplit};
+      reduce_of(l, SLAB_PART, s.nsplit);
+      if (is_top) reduce_of(L - 1, SLAB_PARTL, s.nsplit);
     }
-    if ((rc = flush())) return rc;  // the per-layer kernels below reuse `part`
-    const bool ring = rec1 || ring_t || (PREC == kPrecBF16 && g_dw_ring && !is_top && M == 256 && N == 256);
-    {
-      const Split s = ring ? dw_ring_split(g) : tn_split(g, M, N);
-      int64_t nsplit_used = s.nsplit;
-      TNArgs a;
-      memset(&a, 0, sizeof(a));
-      a.D = ws + lo.dz_off[cur];
-      a.P = rec1 ? (const void*)x : P(l - 1);
-      a.part = part;
-      a.rows_per_batch = g.rows;
-      a.rows_per_split = s.rows_per_split;
-      a.split_stride = split_stride(g, (int64_t)M * N + M);
-      if (rec1) {
-        a.rec_W0 = d->weight[0];
-        a.rec_w0_bstride = d->weights_batched ? (int64_t)F0 * C : 0;
-        a.rec_b0 = d->bias[0];
-        a.rec_b0_bstride = d->weights_batched ? F0 : 0;
-      }
-      a.M = M;
-      a.N = N;
-      a.p_vec = 0;
-      a.w0 = d->w0;
-      a.top = ta;
-      dim3 grid((unsigned)(cdiv(M, TN_BM) * cdiv(N, TN_BN)), (unsigned)s.nsplit, (unsigned)g.nb);
-      const int kcls = PREC != kPrecBF16 || !ring ? SIREN_KCLASS_DW_GEMM
-                       : rec1                     ? SIREN_KCLASS_DW_RING_REC
-                       : ring_t                   ? SIREN_KCLASS_DW_RING_TOP
-                                                  : SIREN_KCLASS_DW_RING;
-      tmark_begin(kcls, st);
-      if constexpr (PREC == kPrecBF16) {
-        const dim3 rg((unsigned)s.nsplit, (unsigned)g.nb);
-        if (rec1) {
-          switch (C) {
-            case 1: hipLaunchKernelGGL((dw_ring_bf16_kernel<1>), rg, dim3(512), 0, st, a); break;
-            case 2: hipLaunchKernelGGL((dw_ring_bf16_kernel<2>), rg, dim3(512), 0, st, a); break;
-            case 3: hipLaunchKernelGGL((dw_ring_bf16_kernel<3>), rg, dim3(512), 0, st, a); break;
-            default: hipLaunchKernelGGL((dw_ring_bf16_kernel<4>), rg, dim3(512), 0, st, a); break;
-          }
-        } else if (ring_t) {
-          if (O == 1) hipLaunchKernelGGL((dw_ring_bf16_kernel<0, 1>), rg, dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((dw_ring_bf16_kernel<0, 2>), rg, dim3(512), 0, st, a);
-        } else if (ring)
-          hipLaunchKernelGGL((dw_ring_bf16_kernel<0>), rg, dim3(512), 0, st, a);
-        else if (is_top) hipLaunchKernelGGL((tn_dw_kernel<PREC, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tn_dw_kernel<PREC, false>), grid, dim3(256), 0, st, a);
-      } else if (g_f32_rows && jvp_tn2_ok(M, N)) {
-        // fp32: jvp_tn2_kernel over the primal stream alone (S = 1: X = sin(P_{l-1}), D = dZ_l):
-        // all 256 dW rows per workgroup, so each X element is formed once per launch
-        JTNArgs j;
-        memset(&j, 0, sizeof(j));
-        const Split s2 = jtn2_split(g, g.rows, N);
-        j.D = a.D;
-        j.P = a.P;
-        j.U = nullptr;
-        j.part = part;
-        j.N = g.rows;
-        j.rows_per_split = s2.rows_per_split;
-        j.split_stride = a.split_stride;
-        j.S = 1;
-        j.Su = 0;
-        j.C = 0;
-        j.M = M;
-        j.Kin = N;
-        j.w0 = d->w0;
-        nsplit_used = s2.nsplit;
-        hipLaunchKernelGGL((jvp_tn2_kernel<false>), dim3((unsigned)cdiv(N, JTN2_BN), (unsigned)s2.nsplit, (unsigned)g.nb),
-                           dim3(512), 0, st, j);
-      } else {
-        hipLaunchKernelGGL((tn_dw_kernel<PREC, false>), grid, dim3(256), 0, st, a);
-      }
-      tmark_end(kcls, st);
-      if ((rc = check_launch("tn_dw"))) return rc;
-      if ((rc = launch_reduce(part, nsplit_used, a.split_stride, g.nb, (int64_t)M * N + M,
-                              (int64_t)M * N, dW[l], db[l], st)))
-        return rc;
-      if (is_top &&
-          (rc = launch_reduce(ta.partL, s.nsplit, ta.partL_stride, g.nb, (int64_t)O * M + O, (int64_t)O * M,
-                              dW[g.L - 1], db[g.L - 1], st)))
-        return rc;
-    }
-    {
-      NTArgs a;
-      memset(&a, 0, sizeof(a));
-      a.A = ws + lo.dz_off[cur];
-      a.W = saved + lo.wt_op_off[l];
-      a.bias = nullptr;
-      a.Paux = rec1 ? nullptr : P(l - 1);
-      a.C = ws + lo.dz_off[cur ^ 1];
-      a.rows_per_batch = g.rows;
-      a.w_bstride = d->weights_batched ? (int64_t)M * N : 0;
-      a.bias_bstride = 0;
-      a.K = M;
-      a.N = N;
-      a.lda = M;
-      a.a_vec = 0;
-      a.w0 = d->w0;
-      a.top = ta;
-      a.stagger = g_dx_stagger ? 1 : 0;
-      const int64_t bot_stride = split_stride(g, (int64_t)F0 * C + F0);
-      if (is_bot) {
-        a.bot.x = x;
-        a.bot.W0 = d->weight[0];
-        a.bot.w0_bstride = d->weights_batched ? (int64_t)F0 * C : 0;
-        a.bot.b0 = d->bias[0];
-        a.bot.b0_bstride = d->weights_batched ? F0 : 0;
-        a.bot.part = part;
-        a.bot.split_stride = bot_stride;
-        a.bot.C = C;
-      }
-      if constexpr (PREC == kPrecBF16) {
-        if (is_bot && ring_bot) {
-          a.C = dx;  // [rows, C] f32, or not written
-          rc = launch_dx_ring_bot(a, g.nb, C, dx != nullptr, rec1, SIREN_KCLASS_DX_RING_BOT, st);
-        } else if (ring_t) {
-          tmark_begin(SIREN_KCLASS_DX_RING_TOP, st);
-          if (O == 1) hipLaunchKernelGGL((dx_ring_bf16_kernel<0, false, false, 1>), ring_grid(a, g.nb), dim3(512), 0, st, a);
-          else hipLaunchKernelGGL((dx_ring_bf16_kernel<0, false, false, 2>), ring_grid(a, g.nb), dim3(512), 0, st, a);
-          tmark_end(SIREN_KCLASS_DX_RING_TOP, st);
-          rc = check_launch("dx_ring top");
-        } else if (is_top && is_bot) rc = launch_nt<PREC, MODE_DX, true, true>(a, g.nb, SIREN_KCLASS_DX_GEMM, st);
-        else if (is_top) rc = launch_nt<PREC, MODE_DX, true, false>(a, g.nb, SIREN_KCLASS_DX_GEMM, st);
-        else if (is_bot) rc = launch_nt<PREC, MODE_DX, false, true>(a, g.nb, SIREN_KCLASS_DX_GEMM, st);
-        else rc = launch_nt<PREC, MODE_DX>(a, g.nb, SIREN_KCLASS_DX_GEMM, st);
-      } else {
-        rc = launch_nt<PREC, MODE_DX>(a, g.nb, SIREN_KCLASS_DX_GEMM, st);
-      }
-      if (rc) return rc;
-      if (is_bot) {
-        const int64_t nslab = ring_bot ? ring_grid(a, g.nb).x : nt_grid(a, g.nb, PREC).x;
-        if ((rc = launch_reduce(part, nslab, bot_stride, g.nb, (int64_t)F0 * C + F0, (int64_t)F0 * C, dW[0],
-                                db[0], st)))
-          return rc;
-        return SIREN_OK;  // first layer done
-      }
-      cur ^= 1;
+    {  // input gradient
+#define SIREN_DX_BOT(CC, DX, REC) SIREN_K(dx_ring_bf16_kernel<CC, DX, REC, 0>)
+      static const Kernel<NTArgs> low[2][2][4] = {{SIREN_C4(SIREN_DX_BOT, false, false), SIREN_C4(SIREN_DX_BOT, true, false)},
+                                                  {SIREN_C4(SIREN_DX_BOT, false, true), SIREN_C4(SIREN_DX_BOT, true, true)}};
+#undef SIREN_DX_BOT
+      static const Kernel<NTArgs> mid[3] = {SIREN_K(dx_ring_bf16_kernel<0, false, false, 0>),
+                                            SIREN_K(dx_ring_bf16_kernel<0, false, false, 1>),
+                                            SIREN_K(dx_ring_bf16_kernel<0, false, false, 2>)};
+      const NTForm form = is_top || is_bot ? NT_TILED : nt_form(prec, MODE_DX, M, N);
+      const dim3 rg = ring_grid(g.rows, g.nb);
+      Launch& a =
+          is_bot && ring_bot ? p.add(K_DX_RING, low[rec1 ? 1 : 0][want_dx ? 1 : 0][c4], "dx_ring first-layer",
+                                     SIREN_KCLASS_DX_RING_BOT, l, rg, 512)
+          : ring_t           ? p.add(K_DX_RING, mid[topo], "dx_ring top", SIREN_KCLASS_DX_RING_TOP, l, rg, 512)
+          : form == NT_RING  ? p.add(K_DX_RING, mid[0], "dx_ring", SIREN_KCLASS_DX_RING, l, rg, 512)
+          : form == NT_ROWS
+              ? p.add(K_DX_ROWS, kRows[1], "f32 rows dx", SIREN_KCLASS_DX_GEMM, l, rows_grid(g.rows, g.nb), 512)
+              : p.add(K_DX_TILED, nt_kernel(prec, MODE_DX, M, is_top, is_bot), kNTNames[MODE_DX], SIREN_KCLASS_DX_GEMM, l,
+                      nt_grid(g.rows, M, N, g.nb, prec), 512);
+      a.top = is_top;
+      a.bot = is_bot;
+      a.rec = rec1;
+      a.dx_out = is_bot && ring_bot;  // [rows, C] f32, or not written
+      p.cur ^= 1;
+      if (!is_bot) continue;
+      a.out[0] = {SLAB_PART, 0, a.grid.x};  // one first-layer slab per workgroup; first layer done
+      a.reduce = RED_OWN;
+      reduce_of(0, SLAB_PART, a.grid.x);
+      return p;
     }
   }
-  if ((rc = flush())) return rc;
+  reduce_pending();
   // First layer.
   if (wide_input(d)) {
-    const int F0 = d->dims[1], C = d->dims[0];
+    static const Kernel<TNArgs> raw[2] = {SIREN_K(tn_dw_kernel<0, true, false>), SIREN_K(tn_dw_kernel<1, true, false>)};
     const Split s = tn_split(g, F0, C);
-    TNArgs a;
-    a.D = ws + lo.dz_off[cur];
-    a.P = x;
-    a.part = part;
-    a.rows_per_batch = g.rows;
-    a.rows_per_split = s.rows_per_split;
-    a.split_stride = split_stride(g, (int64_t)F0 * C + F0);
-    a.M = F0;
-    a.N = C;
-    a.p_vec = (C % 4 == 0) && aligned16(x);
-    dim3 grid((unsigned)(cdiv(F0, TN_BM) * cdiv(C, TN_BN)), (unsigned)s.nsplit, (unsigned)g.nb);
-    hipLaunchKernelGGL((tn_dw_kernel<PREC, true>), grid, dim3(256), 0, st, a);
-    if ((rc = check_launch("tn_dw first"))) return rc;
-    if ((rc = launch_reduce(part, s.nsplit, a.split_stride, g.nb, (int64_t)F0 * C + F0,
-                            (int64_t)F0 * C, dW[0], db[0], st)))
-      return rc;
-    if (dx) {
-      NTArgs n;
-      n.A = ws + lo.dz_off[cur];
-      n.W = saved + lo.wt_op_off[0];
-      n.bias = nullptr;
-      n.Paux = nullptr;
-      n.C = dx;
-      n.rows_per_batch = g.rows;
-      n.w_bstride = d->weights_batched ? (int64_t)F0 * C : 0;
-      n.bias_bstride = 0;
-      n.K = F0;
-      n.N = C;
-      n.lda = F0;
-      n.a_vec = 0;
-      n.w0 = d->w0;
-      if ((rc = launch_nt<PREC, MODE_DXLIN>(n, g.nb, 0, st))) return rc;
-    }
-  } else {
-    const Split s = valu_split(g);
-    FirstBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dZ = ws + lo.dz_off[cur];
-    a.x = x;
-    a.ffB = d->ff_B;
-    a.ffin = d->ff_B ? d->ff_in : 0;
-    a.W = d->weight[0];
-    a.dx = dx;
-    a.part = part;
-    a.rows_per_batch = g.rows;
-    a.rows_per_split = s.rows_per_split;
-    a.F = d->dims[1];
-    a.C = d->dims[0];
-    a.split_stride = split_stride(g, (int64_t)a.F * a.C + a.F);
-    a.w_bstride = d->weights_batched ? (int64_t)d->dims[1] * d->dims[0] : 0;
-    if ((rc = dispatch_first_bwd<PREC>(a, s.nsplit, g.nb, st))) return rc;
-    if ((rc = launch_reduce(part, s.nsplit, a.split_stride, g.nb, (int64_t)a.F * a.C + a.F,
-                            (int64_t)a.F * a.C, dW[0], db[0], st)))
-      return rc;
+    Launch& a = p.add(K_DW_TILED, raw[prec], "tn_dw first", 0, 0,
+                      dim3((unsigned)(cdiv(F0, TN_BM) * cdiv(C, TN_BN)), (unsigned)s.nsplit, nb), 256);
+    writes(a, 0, s);
+    a.p_vec = C % 4 == 0 && x_aligned16;
+    reduce_of(0, SLAB_PART, s.nsplit);
+    if (want_dx)
+      p.add(K_DX_TILED, nt_kernel(prec, MODE_DXLIN, F0), kNTNames[MODE_DXLIN], 0, 0, nt_grid(g.rows, F0, C, g.nb, prec), 512)
+          .dx_out = true;
+    return p;
   }
+  static const Kernel<FirstBwdArgs> narrow[2][3] = {SIREN_IT(first_bwd_kernel, 0, 4), SIREN_IT(first_bwd_kernel, 1, 4)};
+  static const Kernel<FirstBwdArgs> k16[2][2] = {{SIREN_K(first_bwd_kernel<0, 1, 16>), SIREN_K(first_bwd_kernel<0, 2, 16>)},
+                                                 {SIREN_K(first_bwd_kernel<1, 1, 16>), SIREN_K(first_bwd_kernel<1, 2, 16>)}};
+  static const Kernel<FirstBwdArgs> wide[2][2] = {{SIREN_K(first_bwd_wide_kernel<0, 0>), SIREN_K(first_bwd_wide_kernel<0, 16>)},
+                                                  {SIREN_K(first_bwd_wide_kernel<1, 0>), SIREN_K(first_bwd_wide_kernel<1, 16>)}};
+  static const Kernel<FirstBwdArgs> mfma = SIREN_K(first_bwd_wide_mfma_kernel), dxw = SIREN_K(first_dx_wide_kernel);
+  const Split s = valu_split(g);
+  const dim3 grid((unsigned)s.nsplit, nb);
+  const bool mfma_ok = bf16 && F0 == 256 && s.rows_per_split % 32 == 0;
+  // 5..16 inputs: the weight gradient without dx; the input gradient (bf16 mode) as its own MFMA launch
+  const bool split_dx = C > 4 && F0 <= 256 && (!want_dx || (bf16 && F0 == 256));
+  if (d->ff_B && !(mfma_ok && C > 4 && !want_dx)) {
+    p.error = "fourier input: first-layer backward needs the bf16 wide MFMA path and no dx";
+    return p;
+  }
+  Launch& a =
+      d->ff_B    ? p.add(K_FIRST, mfma, "first_bwd_wide_mfma (fourier input)", 0, 0, grid, 256)  // forms the features itself
+      : C <= 4   ? p.add(K_FIRST, narrow[prec][it_index(F0)], "first_bwd", 0, 0, grid, 256)
+      : split_dx ? p.add(K_FIRST, mfma_ok ? mfma : wide[prec][C == 16 ? 1 : 0], want_dx ? "first_bwd_wide" : "first_bwd", 0,
+                         0, grid, 256)
+                 : p.add(K_FIRST, k16[prec][F0 <= 256 ? 0 : 1], "first_bwd", 0, 0, grid, 256);
+  writes(a, 0, s);
+  a.dx_out = want_dx && !split_dx;
+  if (want_dx && split_dx) {
+    Launch& x = p.add(K_FIRST, dxw, "first_bwd", 0, 0, dim3((unsigned)cdiv(cdiv(g.rows, 32), 4), nb), 256);
+    x.rows_per_split = s.rows_per_split;
+    x.dx_out = true;
+  }
+  reduce_of(0, SLAB_PART, s.nsplit);
+  return p;
+}
+
+// The plan as text, one line per launch (siren_mlp_backward_plan).
+std::string plan_text(const BwdPlan& p) {
+  static const char* const outs[] = {"last_bwd", "tiled", "ring"};
+  static const char* const firsts[] = {"ring", "tiled", "mfma", "valu"};
+  static const char* const slabs[] = {"", "part", "part2", "partL", "partB"};
+  static const char* const reds[] = {"", " reduce=own", " reduce=next_pair", " reduce=flush"};
+  char buf[256];
+  snprintf(buf, sizeof(buf), "# out=%s first=%s xcopy=%d launches=%d\n", outs[p.out], firsts[p.first], p.copy_x ? 1 : 0, p.n);
+  std::string t = buf;
+  for (int i = 0; i < p.n; ++i) {
+    const Launch& s = p.steps[i];
+    const SlabUse* u = s.kern == K_REDUCE_MULTI ? p.steps[s.src].out : s.out;
+    int k = snprintf(buf, sizeof(buf), "%s class=%d layer=%d grid=(%u,%u,%u) block=%u", s.sym, s.kclass, s.layer, s.grid.x,
+                     s.grid.y, s.grid.z, s.block);
+    if (u[0].buf != SLAB_NONE) k += snprintf(buf + k, sizeof(buf) - k, " slab=%s", slabs[u[0].buf]);
+    if (u[1].buf != SLAB_NONE) k += snprintf(buf + k, sizeof(buf) - k, "+%s", slabs[u[1].buf]);
+    if (u[0].buf != SLAB_NONE) k += snprintf(buf + k, sizeof(buf) - k, " nsplit=%lld", (long long)u[0].nsplit);
+    if (u[1].buf != SLAB_NONE) k += snprintf(buf + k, sizeof(buf) - k, "+%lld", (long long)u[1].nsplit);
+    if (s.kern == K_DW_TILED && s.layer == 0) k += snprintf(buf + k, sizeof(buf) - k, " p_vec=%d", s.p_vec ? 1 : 0);
+    snprintf(buf + k, sizeof(buf) - k, "%s\n", reds[s.reduce]);
+    t += buf;
+  }
+  return t;
+}
+
+// One backward call's buffers, and the launcher of every kind of plan step.
+struct BwdWalk {
+  const siren_mlp_desc* d;
+  const Geo& g;
+  const Layout& lo;
+  const BwdPlan& p;
+  const float *x, *dy, *dy_scale;
+  const char* saved;
+  char* ws;
+  float *const *dW, *const *db;
+  float* dx;
+  hipStream_t st;
+  TopArgs ta;  // the output layer folded into the top hidden layer's kernels (zeros: it is not)
+
+  const void* P(int l) const { return saved + lo.saved_off[l]; }
+  char* dz(int k) const { return ws + lo.dz_off[k]; }
+  float* slab(Slab s) const {
+    const int64_t off[] = {0, lo.part_off, lo.part2_off, lo.partL_off, lo.partB_off};
+    return (float*)(ws + off[s]);
+  }
+  void set_top() {
+    memset(&ta, 0, sizeof(ta));
+    if (p.out == OUT_LAST_BWD) return;
+    const int L = g.L;
+    ta.Ptop = P(L - 2);
+    ta.dy = dy;
+    ta.dy_scale = dy_scale;
+    ta.WL = d->weight[L - 1];
+    ta.wl_bstride = bstride(d, (int64_t)d->dims[L] * d->dims[L - 1]);
+    ta.partL = slab(SLAB_PARTL);
+    ta.partL_stride = split_stride(g, slab_elems(d, L - 1));
+    ta.O = d->dims[L];
+  }
+  // the slabs launch i wrote, as the segments of a reduce_multi launch or of a pair launch's tail
+  ReduceMultiArgs segments(int i) const {
+    ReduceMultiArgs r;
+    memset(&r, 0, sizeof(r));
+    for (int k = 0; i >= 0 && k < 2 && p.steps[i].out[k].buf != SLAB_NONE; ++k) {
+      const SlabUse& u = p.steps[i].out[k];
+      const int64_t sz = slab_elems(d, u.layer);
+      ReduceSeg& s = r.seg[r.nseg++];
+      s.part = slab(u.buf);
+      s.nsplit = (int)u.nsplit;
+      s.split_stride = split_stride(g, sz);
+      s.total = (int)(g.nb * sz);
+      s.slab = (int)sz;
+      s.n_first = (int)(sz - d->dims[u.layer + 1]);
+      s.out0 = dW[u.layer];
+      s.out1 = db[u.layer];
+      s.blocks = (int)reduce_blocks(g.nb, sz);
+    }
+    return r;
+  }
+  template <class... Args>
+  int go(const Launch& s, const Args&... a) const {
+    return launch_kernel(Kernel<Args...>{(void (*)(Args...))s.fn, s.sym}, s.grid, s.block, s.kclass, s.what, st, a...);
+  }
+  TNArgs dw_args(const Launch& s) const {
+    const int l = s.layer;
+    TNArgs w = tn_args(d, g, l, dz(s.cur), l && !s.rec ? P(l - 1) : x, slab(s.out[0].buf), s.rows_per_split);
+    if (s.rec) {  // P_0 rebuilt from x
+      w.rec_W0 = d->weight[0];
+      w.rec_w0_bstride = bstride(d, (int64_t)d->dims[1] * d->dims[0]);
+      w.rec_b0 = d->bias[0];
+      w.rec_b0_bstride = bstride(d, d->dims[1]);
+    }
+    w.p_vec = s.p_vec;
+    w.top = ta;
+    return w;
+  }
+  NTArgs dx_args(const Launch& s) const {
+    const int l = s.layer;
+    NTArgs a = nt_args(d, g, l, false, dz(s.cur), saved + lo.wt_op_off[l], s.dx_out ? (void*)dx : dz(s.cur ^ 1));
+    a.Paux = s.rec || l == 0 ? nullptr : P(l - 1);
+    a.top = ta;
+    a.stagger = p.stagger;
+    if (s.bot) {  // the first layer folded in: its slabs are the launch's layer-0 ones
+      const SlabUse& u = s.out[1].buf != SLAB_NONE ? s.out[1] : s.out[0];
+      a.bot.x = x;
+      a.bot.W0 = d->weight[0];
+      a.bot.w0_bstride = bstride(d, (int64_t)d->dims[1] * d->dims[0]);
+      a.bot.b0 = d->bias[0];
+      a.bot.b0_bstride = bstride(d, d->dims[1]);
+      a.bot.part = slab(u.buf);
+      a.bot.split_stride = split_stride(g, slab_elems(d, 0));
+      a.bot.C = d->dims[0];
+    }
+    return a;
+  }
+
+  int run(const Launch& s) {
+    const int l = s.layer;
+    switch (s.kern) {
+      case K_XCOPY:
+        if (hipMemcpyAsync(ws + lo.xcopy_off, x, g.total * d->dims[0] * sizeof(float), hipMemcpyDeviceToDevice, st) !=
+            hipSuccess)
+          return fail(SIREN_ELAUNCH, "x copy: %s", hipGetErrorString(hipGetLastError()));
+        x = (const float*)(ws + lo.xcopy_off);
+        return SIREN_OK;
+      case K_LAST_BWD: {
+        LastBwdArgs a;
+        a.P = P(l - 1);
+        a.W = d->weight[l];
+        a.b = d->bias[l];
+        a.dy = dy;
+        a.dy_scale = dy_scale;
+        a.dZ = dz(s.cur);
+        a.part = slab(s.out[0].buf);
+        a.rows_per_batch = g.rows;
+        a.rows_per_split = s.rows_per_split;
+        a.F = d->dims[l];
+        a.O = d->dims[l + 1];
+        a.split_stride = split_stride(g, slab_elems(d, l));
+        a.w_bstride = bstride(d, (int64_t)a.O * a.F);
+        a.b_bstride = bstride(d, a.O);
+        a.sine_out = d->outermost_linear ? 0 : 1;
+        a.w0 = d->w0;
+        return go(s, a);
+      }
+      case K_REDUCE: {
+        const int64_t sz = slab_elems(d, l);
+        return launch_reduce(slab(s.out[0].buf), s.out[0].nsplit, split_stride(g, sz), g.nb, sz, sz - d->dims[l + 1], dW[l],
+                             db[l], st);
+      }
+      case K_REDUCE_MULTI:
+        return go(s, segments(s.src));
+      case K_PAIR: {
+        TNArgs w = dw_args(s);
+        NTArgs a = dx_args(s);
+        w.pair_roles = p.pair_roles;
+        w.prof = a.prof = ring_profile_next();
+        return go(s, a, w, segments(s.src));  // (the previous pair launch's slabs: reduced in this one's tail)
+      }
+      case K_DW_TILED:
+      case K_DW_RING:
+        return go(s, dw_args(s));
+      case K_DW_ROWS: {
+        const TNArgs w = dw_args(s);
+        JTNArgs j;
+        memset(&j, 0, sizeof(j));
+        j.D = w.D;
+        j.P = w.P;
+        j.part = w.part;
+        j.N = g.rows;
+        j.rows_per_split = s.rows_per_split;
+        j.split_stride = w.split_stride;
+        j.S = 1;
+        j.M = w.M;
+        j.Kin = w.N;
+        j.w0 = d->w0;
+        return go(s, j);
+      }
+      case K_DX_TILED:
+      case K_DX_RING:
+        return go(s, dx_args(s));
+      case K_DX_ROWS:
+        return launch_rows(MODE_DX, dx_args(s), g.nb, s.kclass, st);
+      case K_FIRST: {
+        FirstBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.dZ = dz(s.cur);
+        a.x = x;
+        a.ffB = d->ff_B;
+        a.ffin = d->ff_B ? d->ff_in : 0;
+        a.W = d->weight[0];
+        a.dx = s.dx_out ? dx : nullptr;
+        a.part = slab(SLAB_PART);
+        a.rows_per_batch = g.rows;
+        a.rows_per_split = s.rows_per_split;
+        a.F = d->dims[1];
+        a.C = d->dims[0];
+        a.split_stride = split_stride(g, slab_elems(d, 0));
+        a.w_bstride = bstride(d, (int64_t)a.F * a.C);
+        return go(s, a);
+      }
+    }
+    return SIREN_OK;
+  }
+};
+
+int backward_impl(const siren_mlp_desc* d, const float* x, const float* dy, const char* saved, char* ws,
+                  float* const* dW, float* const* db, float* dx, hipStream_t st, const float* dy_scale = nullptr) {
+  const Geo g = geo_of(d);
+  const Layout lo = layout_of(d);
+  const BwdPlan p = plan_backward(d, g, lo, dx != nullptr, aligned16(x), aligned16(dy));
+  if (p.error) return fail(SIREN_EINVAL, "%s", p.error);
+  BwdWalk w{d, g, lo, p, x, dy, dy_scale, saved, ws, dW, db, dx, st, {}};
+  w.set_top();
+  for (int i = 0; i < p.n; ++i)
+    if (int rc = w.run(p.steps[i])) return rc;
   return SIREN_OK;
 }
 

@@ -156,11 +156,22 @@ int siren_mlp_backward_ex(const siren_mlp_desc* d, const float* x, const float* 
   for (int l = 0; l < d->num_layers; ++l)
     if (!dweight[l] || !dbias[l]) return fail(SIREN_EINVAL, "layer %d: null gradient output", l);
   if (d->ff_B && dx) return fail(SIREN_EINVAL, "fourier input: no input gradient (dx must be NULL)");
-  hipStream_t st = (hipStream_t)stream;
   g_err.clear();
-  if (d->prec == SIREN_PREC_BF16)
-    return backward_impl<kPrecBF16>(d, x, dy, (const char*)saved, (char*)workspace, dweight, dbias, dx, st, dy_scale);
-  return backward_impl<kPrecF32>(d, x, dy, (const char*)saved, (char*)workspace, dweight, dbias, dx, st, dy_scale);
+  return backward_impl(d, x, dy, (const char*)saved, (char*)workspace, dweight, dbias, dx, (hipStream_t)stream, dy_scale);
+}
+
+int64_t siren_mlp_backward_plan(const siren_mlp_desc* d, int flags, char* out, int64_t cap) {
+  if (siren_mlp_check(d)) return -1;
+  if (d->ff_B && (flags & 1)) return fail(SIREN_EINVAL, "fourier input: no input gradient (dx must be NULL)"), -1;
+  const BwdPlan p = plan_backward(d, geo_of(d), layout_of(d), flags & 1, flags & 2, flags & 4);
+  if (p.error) return fail(SIREN_EINVAL, "%s", p.error), -1;
+  const std::string t = plan_text(p);
+  if (out && cap > 0) {
+    const size_t n = std::min<size_t>(t.size(), (size_t)cap - 1);
+    memcpy(out, t.data(), n);
+    out[n] = 0;
+  }
+  return (int64_t)t.size() + 1;
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <algorithm>
 #include <cstdarg>
+#include <cassert>
 
 #include "../../include/siren_mri_amd.h"
 #include "siren_valu.hip"
@@ -30,9 +31,9 @@ using namespace siren;
 // extern "C" block of entry points. rt_common.hip comes first (errors, geometry, options, timing);
 // rt_mlp_entry.hip and rt_jvp.hip build on rt_mlp.hip; the others need rt_common.hip alone.
 // The order is also the order in which the compiler first meets each kernel template's use, which
-// is the order of the kernels in the code object: rt_hyper.hip and rt_f64.hip stand between the
-// stack's launch plan and its entry points because that keeps the code object as it was before the
-// runtime was split into parts. Reordering the parts is harmless but reorders the code object.
+// is the order of the kernels in the code object (for the stack's kernels: the order of rt_mlp.hip's
+// kernel tables). Reordering the parts or the tables is harmless but reorders the code object, so
+// two builds are compared kernel by kernel (tools/compare_code_objects.py), not by hash.
 #include "rt_common.hip"
 #include "rt_mlp.hip"
 #include "rt_hyper.hip"

@@ -102,7 +102,7 @@ def test_config_options():
 # name -> (min, max, default) of every integer option of siren_config_set / siren_config_get
 _ON = ("fused_forward", "fused_backward", "ring_output_fusion", "fused_forward_pipe", "fused_forward_reg", "dw_ring",
        "dx_ring", "pair_tail_reduce", "jvp_adj", "f32_rows", "jvp_tan", "jvp_tn2", "pair_ring")
-_OFF = ("fuse_output_layer", "freg_magic", "bwd_ring", "dx_stagger", "debug_keep_p0")
+_OFF = ("fuse_output_layer", "freg_magic", "dx_stagger", "debug_keep_p0")
 OPTIONS = {**{k: (0, 1, 1) for k in _ON}, **{k: (0, 1, 0) for k in _OFF},
            "debug_pair_roles": (0, 3, 3), "wrw_dma": (0, 3, 2), "conv_dma": (0, 2, 2), "debug_fwd_skip": (0, 31, 0)}
 
@@ -126,6 +126,15 @@ def test_option_table_row(key):
     finally:
         assert lib.siren_config_set(k, default) == 0
     assert lib.siren_config_get(k) == default
+
+
+def test_retired_option_is_unknown():
+    """bwd_ring went with its kernel: setting it fails like any unknown key."""
+    lib = _native.load_library()
+    for v in (0, 1):
+        assert lib.siren_config_set(b"bwd_ring", v) != 0
+        assert "unknown option" in _native.last_error()
+    assert lib.siren_config_get(b"bwd_ring") == -1
 
 
 @pytest.mark.parametrize("key", [b"debug_ring_profile", b"debug_fused_profile"])
