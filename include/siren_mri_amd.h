@@ -511,6 +511,47 @@ int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const flo
                                float noise, const float* g, float* dpred, void* stream);
 
 /*
+ * Batched 2-D FFT of square slices, and the image-domain member of the k-space loss family
+ * (siren_kfft.hip). A slice is [side * side, 2] float32 (real, imaginary), pixels row-major as
+ * lin2img lays them out; side is 8, 16, 32, 64 or 128, and one workgroup transforms one slice in LDS.
+ * siren_kspace_fft2  out = fft2(x) (inverse == 0, unscaled) or ifft2(x) (inverse != 0, scaled by
+ *                    1 / side^2): torch.fft's conventions, x and out [batch, side * side, 2], one launch.
+ *                    Stands in for the torch.fft.ifft2 calls of loss_functions.py:205-206 where a
+ *                    transform alone is wanted; no autograd formula goes with it.
+ * siren_kspace_ift_loss_forward  replaces ift_image_mse (loss_functions.py:192-229):
+ *                      *loss = img_weight    sum m (|ifft2 y| - |ifft2 t|)^2
+ *                            + l1_weight     sum |y|           (complex magnitudes)
+ *                            + kspace_weight sum (y - t)^2     (both channels)
+ *                    of y = DC(pred) (k0 and mask given, [batch, 2, npix]; siren_dc_forward's arithmetic)
+ *                    or of pred (both NULL), t = tgt; the reference's weights are 1, 1e-8 and 0.0025.
+ *                    img_mask (or NULL) multiplies the squared magnitude differences: [side, side] with
+ *                    img_mask_batch_stride 0, or [batch, side, side] with stride side * side. One launch,
+ *                    deterministic summation order (a fixed tree per slice, then the slices in order);
+ *                    workspace as siren_sse_forward's (siren_sse_workspace_bytes()), one slot per slice:
+ *                    batch <= (siren_sse_workspace_bytes() - 256) / 4. Nothing is kept for the backward.
+ * siren_kspace_ift_loss_backward  dpred = g[0] dL/dy coef(mask) (coef = 1 without DC), recomputed from
+ *                    pred and tgt in one launch: the backward of abs, ifft2 (its adjoint is fft2 over
+ *                    side^2), the sums and the data consistency in one pass. At zero the gradients are
+ *                    torch autograd's: the gradient of a complex magnitude is 0 at 0. A slice with
+ *                    y == t bitwise has an image term and an image gradient of exactly 0.
+ */
+typedef struct siren_kift_desc {
+  float img_weight;    /* of the image-domain SSE: 1 in the reference          */
+  float l1_weight;     /* of sum |y|: 1e-8                                     */
+  float kspace_weight; /* of the k-space SSE: 0.0025                           */
+} siren_kift_desc;
+
+int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream);
+int siren_kspace_ift_loss_forward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
+                                  const float* tgt, const float* img_mask, int64_t img_mask_batch_stride,
+                                  int64_t batch, int side, float noise, float* loss, void* workspace,
+                                  int64_t ws_bytes, void* stream);
+int siren_kspace_ift_loss_backward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
+                                   const float* tgt, const float* img_mask, int64_t img_mask_batch_stride,
+                                   int64_t batch, int side, float noise, const float* g, float* dpred,
+                                   void* stream);
+
+/*
  * Gaussian Fourier features (replaces GaussianFourierFeatureTransform.forward, features.py:31-41):
  * out [rows, 2 m] = cat(sin(2 pi x B), cos(2 pi x B)) for x [rows, cin], B [cin, m] (device float32),
  * one launch. Feeds the SIREN's wide first layer (5..16 inputs on the register-resident forward).

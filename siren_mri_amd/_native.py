@@ -101,6 +101,19 @@ class SirenKlossDesc(ctypes.Structure):
     ]
 
 
+class SirenKiftDesc(ctypes.Structure):
+    """Mirror of ``siren_kift_desc`` (include/siren_mri_amd.h)."""
+
+    _fields_ = [
+        ("img_weight", ctypes.c_float),
+        ("l1_weight", ctypes.c_float),
+        ("kspace_weight", ctypes.c_float),
+    ]
+
+
+# sides of siren_kspace_fft2 and siren_kspace_ift_loss_* (one workgroup transforms one slice in LDS)
+KFFT_SIDES = (8, 16, 32, 64, 128)
+
 HYPER_MAXG = 32
 HYPER_MAXD = 4
 
@@ -166,6 +179,7 @@ def _signatures():
     pvp, pi64 = ctypes.POINTER(vp), ctypes.POINTER(i64)
     P, LP, HP = ctypes.POINTER(SirenMLPDesc), ctypes.POINTER(SirenLossDesc), ctypes.POINTER(SirenHyperDesc)
     KP, AP = ctypes.POINTER(SirenKlossDesc), ctypes.POINTER(SirenAdamDesc)
+    KIP = ctypes.POINTER(SirenKiftDesc)
     fwd = [P, vp, vp, vp, i64, vp, i64, vp]                   # desc, x, y, saved, bytes, workspace, bytes, stream
     bwd = [P, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]     # desc, x, dy, saved, .., dweight, dbias, dx, stream
     return {
@@ -230,6 +244,9 @@ def _signatures():
         "siren_kspace_sse_backward": (ci, [vp, vp, vp, i64, i64, ci, f32, vp, f32, vp, vp]),
         "siren_kspace_loss_forward": (ci, [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, i64, vp]),
         "siren_kspace_loss_backward": (ci, [ci, KP, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, vp]),
+        "siren_kspace_fft2": (ci, [vp, vp, i64, ci, ci, vp]),
+        "siren_kspace_ift_loss_forward": (ci, [KIP, vp, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, i64, vp]),
+        "siren_kspace_ift_loss_backward": (ci, [KIP, vp, vp, vp, vp, vp, i64, i64, ci, f32, vp, vp, vp]),
         "siren_fourier_features": (ci, [vp, vp, i64, ci, ci, vp, vp]),
         "siren_sincos_f32": (ci, [vp, vp, vp, i64, ci, vp]),
         "siren_last_error": (cstr, []),

@@ -1,5 +1,6 @@
 // rt_loss.hip — image and k-space losses, data consistency, Fourier features and the sin/cos probe
-// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip). Included by siren_runtime.hip.
+// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_kfft.hip). Included by
+// siren_runtime.hip.
 namespace {
 
 // one launch of KERNEL<kind> (kind checked by kloss_check)
@@ -50,6 +51,58 @@ KlossArgs kloss_args(const siren_kloss_desc* d, const float* pred, const float* 
   a.divisor = d->divisor;
   a.mag_weight = d->mag_weight;
   a.phase_weight = d->phase_weight;
+  return a;
+}
+
+// one launch of KERNEL<log2 side>, one workgroup per slice (side checked by kfft_log2)
+#define KFFT_LAUNCH(KERNEL, lg, slices, stream, a)                                                                 \
+  do {                                                                                                             \
+    switch (lg) {                                                                                                  \
+      case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(slices), dim3(KfGeom<3>::T), 0, stream, a); break;                \
+      case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(slices), dim3(KfGeom<4>::T), 0, stream, a); break;                \
+      case 5: hipLaunchKernelGGL(KERNEL<5>, dim3(slices), dim3(KfGeom<5>::T), 0, stream, a); break;                \
+      case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(slices), dim3(KfGeom<6>::T), 0, stream, a); break;                \
+      default: hipLaunchKernelGGL(KERNEL<7>, dim3(slices), dim3(KfGeom<7>::T), 0, stream, a); break;               \
+    }                                                                                                              \
+  } while (0)
+
+// log2 of a supported side (8, 16, 32, 64, 128), or -1
+int kfft_log2(int side) {
+  for (int lg = 3; lg <= 7; ++lg)
+    if (side == (1 << lg)) return lg;
+  return -1;
+}
+
+// the argument checks the two loss entry points share; 0 or SIREN_EINVAL (message set)
+int kift_check(const char* what, const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
+               const float* tgt, const float* img_mask, int64_t img_mask_bstride, int64_t batch, int side) {
+  if (kfft_log2(side) < 0) return fail(SIREN_EINVAL, "%s: side %d is not one of 8, 16, 32, 64, 128", what, side);
+  if (!desc) return fail(SIREN_EINVAL, "%s: null descriptor", what);
+  if (!pred || !tgt) return fail(SIREN_EINVAL, "%s: null pointer", what);
+  if ((!k0) != (!mask)) return fail(SIREN_EINVAL, "%s: k0 and mask go together (data consistency)", what);
+  if (batch < 1 || batch > KF_MAX_SLICES)
+    return fail(SIREN_EINVAL, "%s: batch %lld outside [1, %d] (one workspace slot per slice)", what, (long long)batch,
+                KF_MAX_SLICES);
+  if (img_mask && img_mask_bstride != 0 && img_mask_bstride != (int64_t)side * side)
+    return fail(SIREN_EINVAL, "%s: img_mask batch stride %lld is neither 0 nor side^2", what,
+                (long long)img_mask_bstride);
+  return SIREN_OK;
+}
+
+KiftArgs kift_args(const siren_kift_desc* d, const float* pred, const float* k0, const float* mask, const float* tgt,
+                   const float* img_mask, int64_t img_mask_bstride, float noise) {
+  KiftArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.k0 = k0;
+  a.mask = mask;
+  a.tgt = tgt;
+  a.img_mask = img_mask;
+  a.img_mask_bstride = img_mask ? img_mask_bstride : 0;
+  a.noise = noise;
+  a.img_weight = d->img_weight;
+  a.l1_weight = d->l1_weight;
+  a.kspace_weight = d->kspace_weight;
   return a;
 }
 }  // namespace
@@ -187,6 +240,53 @@ int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const flo
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KL_THREADS)));
   KLOSS_LAUNCH(kloss_bwd_kernel, kind, blocks, (hipStream_t)stream, a);
   return check_launch("kspace_loss_backward");
+}
+
+int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream) {
+  const int lg = kfft_log2(side);
+  if (lg < 0) return fail(SIREN_EINVAL, "kspace_fft2: side %d is not one of 8, 16, 32, 64, 128", side);
+  if (batch < 0 || batch > 0x7fffffff)
+    return fail(SIREN_EINVAL, "kspace_fft2: bad batch %lld", (long long)batch);
+  if (batch > 0 && (!x || !out)) return fail(SIREN_EINVAL, "kspace_fft2: null pointer");
+  if (batch == 0) return SIREN_OK;
+  KfftArgs a{x, out, inverse ? 1 : 0};
+  KFFT_LAUNCH(kfft2_kernel, lg, (unsigned)batch, (hipStream_t)stream, a);
+  return check_launch("kspace_fft2");
+}
+
+int siren_kspace_ift_loss_forward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
+                                  const float* tgt, const float* img_mask, int64_t img_mask_batch_stride,
+                                  int64_t batch, int side, float noise, float* loss, void* workspace,
+                                  int64_t ws_bytes, void* stream) {
+  if (int rc = kift_check("kspace_ift_loss_forward", desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride, batch,
+                          side))
+    return rc;
+  if (!loss) return fail(SIREN_EINVAL, "kspace_ift_loss_forward: null pointer");
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "kspace_ift_loss_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  static_assert(KF_MAX_SLICES == SSE_MAX_BLOCKS, "the hand-off's slots are siren_sse_workspace_bytes()'s");
+  KiftArgs a = kift_args(desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride, noise);
+  a.out = loss;
+  a.partial = (float*)workspace;
+  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
+  KFFT_LAUNCH(kift_fwd_kernel, kfft_log2(side), (unsigned)batch, (hipStream_t)stream, a);
+  return check_launch("kspace_ift_loss_forward");
+}
+
+int siren_kspace_ift_loss_backward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
+                                   const float* tgt, const float* img_mask, int64_t img_mask_batch_stride,
+                                   int64_t batch, int side, float noise, const float* g, float* dpred,
+                                   void* stream) {
+  if (int rc = kift_check("kspace_ift_loss_backward", desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride,
+                          batch, side))
+    return rc;
+  if (!g || !dpred) return fail(SIREN_EINVAL, "kspace_ift_loss_backward: null pointer");
+  KiftArgs a = kift_args(desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride, noise);
+  a.g = g;
+  a.out = dpred;
+  KFFT_LAUNCH(kift_bwd_kernel, kfft_log2(side), (unsigned)batch, (hipStream_t)stream, a);
+  return check_launch("kspace_ift_loss_backward");
 }
 
 int siren_fourier_features(const float* x, const float* B, int64_t rows, int cin, int m, float* out, void* stream) {

@@ -15,7 +15,9 @@
 image_mse runs on the native k-space op (siren_kspace.hip), with the data consistency of a native
 DataConsistencyInKspace output folded in. The six k-space losses of the
 family run on siren_mri_amd::kspace_loss (siren_kloss.hip: one forward and one backward launch, the
-DC folded in the same way); ift_image_mse and image_l1 are PyTorch compositions.
+DC folded in the same way); ift_image_mse runs on siren_mri_amd::kspace_ift_loss (siren_kfft.hip: the
+two ifft2 and the three sums in one forward launch, one backward launch) for square slices of side
+8 to 128, and is a PyTorch composition otherwise, as image_l1 is.
 
 Deliberate deviation (bug 0.2): the reference builds its high-frequency mask
 on a fixed 128x128 grid, so image_mse(high_freq=True) raises for any other image size; here the
@@ -464,6 +466,172 @@ def _kspace_loss_native(out, tgt, kind):
     return torch.ops.siren_mri_amd.kspace_loss(out, None, None, tgt, kind, 0.0)
 
 
+# The image-domain member of the family and the transform it runs on (siren_kfft.hip), on [B, side^2, 2]
+# (real, imaginary; pixels row-major as lin2img lays them out), side 8, 16, 32, 64 or 128:
+#   siren_mri_amd::kspace_fft2(x, inverse) -> torch.fft.fft2 / ifft2 of the complex slices, as [B, side^2, 2]
+#   siren_mri_amd::kspace_ift_loss(pred, k0?, mask?, tgt, img_mask?, noise, img_weight, l1_weight, kspace_weight)
+#       -> img_weight sum m (|ifft2 y| - |ifft2 t|)^2 + l1_weight sum |y| + kspace_weight sum (y - t)^2
+#   siren_mri_amd::kspace_ift_loss_bwd(the same operands, g, ...) -> dpred
+# One launch each; the backward recomputes everything from its inputs, so the forward saves no residual.
+_LIB.define("kspace_fft2(Tensor x, bool inverse) -> Tensor")
+_LIB.define("kspace_ift_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, float noise, "
+            "float img_weight, float l1_weight, float kspace_weight) -> Tensor")
+_LIB.define("kspace_ift_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, Tensor g, "
+            "float noise, float img_weight, float l1_weight, float kspace_weight) -> Tensor")
+
+# ift_image_mse's constants (loss_functions.py:207-229): image SSE, 1e-8 sum |y|, 0.0025 k-space SSE
+_IFT_WEIGHTS = (1.0, 1e-8, 0.0025)
+
+
+def _kfft_side(n):
+    """The side of an n-pixel slice the transform kernels take, or None."""
+    side = int(round(n ** 0.5))
+    return side if side * side == n and side in _native.KFFT_SIDES else None
+
+
+def _kift_max_batch():
+    """Slices per launch of the loss ops: one slot of the SSE workspace each."""
+    return (int(_native.lib().siren_sse_workspace_bytes()) - 256) // 4
+
+
+def _kfft2_cuda(x, inverse):
+    if x.dim() != 3 or x.shape[-1] != 2 or _kfft_side(x.shape[1]) is None or x.dtype != torch.float32:
+        raise RuntimeError(f"siren_mri_amd.kspace_fft2: x {tuple(x.shape)} {x.dtype} must be float32 [B, side^2, 2] "
+                           f"with side in {_native.KFFT_SIDES}")
+    xc = x.contiguous()
+    out = torch.empty_like(xc)
+    rc = _native.lib().siren_kspace_fft2(xc.data_ptr(), out.data_ptr(), xc.shape[0], _kfft_side(xc.shape[1]),
+                                         1 if inverse else 0, _native.stream_handle(x.device))
+    _native.check(rc, "siren_kspace_fft2")
+    return out
+
+
+def _kfft2_autograd(x, inverse):
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("siren_mri_amd.kspace_fft2 is not differentiable: detach its input (the image-domain "
+                           "loss with a gradient is siren_mri_amd.kspace_ift_loss), or use torch.fft")
+    with torch._C._AutoDispatchBelowAutograd():
+        return torch.ops.siren_mri_amd.kspace_fft2(x, inverse)
+
+
+def _kift_operands(pred, k0, mask, tgt, img_mask):
+    """Contiguous fp32 operands of the two loss ops; img_mask as (tensor or None, its batch stride)."""
+    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
+    side = _kfft_side(n)
+    if c != 2 or side is None:
+        raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: pred {tuple(pred.shape)} must be [B, side^2, 2] with side "
+                           f"in {_native.KFFT_SIDES}")
+    stride = 0
+    if img_mask is not None:
+        if img_mask.dtype != torch.float32 or img_mask.device != pred.device:
+            raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: img_mask must be float32 on {pred.device}")
+        if tuple(img_mask.shape) == (b, side, side) and b > 1:
+            stride = n
+        elif tuple(img_mask.shape) not in ((side, side), (1, side, side)):
+            raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: img_mask {tuple(img_mask.shape)} is neither "
+                               f"[{side}, {side}] nor [{b}, {side}, {side}]")
+        img_mask = img_mask.contiguous()
+    return b, side, pc, kc, mc, tc, img_mask, stride
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _kspace_ift_loss_cuda(pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight):
+    import ctypes
+    b, side, pc, kc, mc, tc, ic, stride = _kift_operands(pred, k0, mask, tgt, img_mask)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    ws = _sse_workspace(pred.device)
+    desc = _native.SirenKiftDesc(img_weight, l1_weight, kspace_weight)
+    rc = _native.lib().siren_kspace_ift_loss_forward(
+        ctypes.byref(desc), pc.data_ptr(), _ptr(kc), _ptr(mc), tc.data_ptr(), _ptr(ic), stride, b, side, float(noise),
+        loss.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
+    _native.check(rc, "siren_kspace_ift_loss_forward")
+    return loss
+
+
+def _kspace_ift_loss_bwd_cuda(pred, k0, mask, tgt, img_mask, g, noise, img_weight, l1_weight, kspace_weight):
+    import ctypes
+    b, side, pc, kc, mc, tc, ic, stride = _kift_operands(pred, k0, mask, tgt, img_mask)
+    if g.numel() != 1 or g.device != pred.device:
+        raise RuntimeError("siren_mri_amd.kspace_ift_loss_bwd: g must be one element on the prediction's device")
+    gc = g.contiguous().to(torch.float32)
+    out = torch.empty_like(pc)
+    desc = _native.SirenKiftDesc(img_weight, l1_weight, kspace_weight)
+    rc = _native.lib().siren_kspace_ift_loss_backward(
+        ctypes.byref(desc), pc.data_ptr(), _ptr(kc), _ptr(mc), tc.data_ptr(), _ptr(ic), stride, b, side, float(noise),
+        gc.data_ptr(), out.data_ptr(), _native.stream_handle(pred.device))
+    _native.check(rc, "siren_kspace_ift_loss_backward")
+    return out
+
+
+class _KspaceIftLossAutograd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight):
+        with torch._C._AutoDispatchBelowAutograd():
+            loss = torch.ops.siren_mri_amd.kspace_ift_loss(pred, k0, mask, tgt, img_mask, noise, img_weight,
+                                                           l1_weight, kspace_weight)
+        ctx.save_for_backward(pred, k0, mask, tgt, img_mask)  # the op's own inputs: no residual is kept
+        ctx.consts = (noise, img_weight, l1_weight, kspace_weight)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 9
+        if torch.is_grad_enabled():
+            raise RuntimeError("siren_mri_amd: double backward through the native image-domain k-space loss is not "
+                               "provided; run it on the expression path (siren_mri_amd.loss_functions."
+                               "set_kspace_loss_native(False))")
+        pred, k0, mask, tgt, img_mask = ctx.saved_tensors
+        dpred = torch.ops.siren_mri_amd.kspace_ift_loss_bwd(pred, k0, mask, tgt, img_mask, g, *ctx.consts)
+        return (dpred,) + (None,) * 8
+
+
+_LIB.impl("kspace_fft2", _kfft2_cuda, "CUDA")
+_LIB.impl("kspace_fft2", _kfft2_autograd, "Autograd")
+_LIB.impl("kspace_ift_loss", _kspace_ift_loss_cuda, "CUDA")
+_LIB.impl("kspace_ift_loss_bwd", _kspace_ift_loss_bwd_cuda, "CUDA")
+_LIB.impl("kspace_ift_loss", lambda pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight:
+          _KspaceIftLossAutograd.apply(pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight),
+          "Autograd")
+torch.library.register_fake("siren_mri_amd::kspace_fft2", lambda x, inverse: torch.empty_like(x), lib=_LIB)
+torch.library.register_fake(
+    "siren_mri_amd::kspace_ift_loss",
+    lambda pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight: pred.new_empty(()), lib=_LIB)
+torch.library.register_fake(
+    "siren_mri_amd::kspace_ift_loss_bwd",
+    lambda pred, k0, mask, tgt, img_mask, g, noise, img_weight, l1_weight, kspace_weight: torch.empty_like(pred),
+    lib=_LIB)
+
+
+def _ift_native_applies(mask, out, tgt):
+    """Whether ift_image_mse of these operands runs on siren_mri_amd::kspace_ift_loss."""
+    if not (_KLOSS_NATIVE and torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3
+            and out.shape[-1] == 2 and tgt.shape == out.shape and tgt.dtype == torch.float32
+            and tgt.device == out.device and not tgt.requires_grad):
+        return False
+    b, side = out.shape[0], _kfft_side(out.shape[1])
+    if side is None or not 1 <= b <= _kift_max_batch():
+        return False
+    return mask is None or (torch.is_tensor(mask) and mask.dtype == torch.float32 and mask.device == out.device
+                            and not mask.requires_grad
+                            and tuple(mask.shape) in ((side, side), (1, side, side), (b, side, side)))
+
+
+def _ift_loss_native(mask, out, tgt):
+    """ift_image_mse on [B, side^2, 2] through the native op, or None when it does not apply."""
+    if not _ift_native_applies(mask, out, tgt):
+        return None
+    src = dc_source(out) if _FUSE_DC else None
+    if src is not None and src[0].shape == out.shape:
+        pred, k0, planes, noise = src
+        return torch.ops.siren_mri_amd.kspace_ift_loss(pred, k0, planes, tgt, mask, noise, *_IFT_WEIGHTS)
+    return torch.ops.siren_mri_amd.kspace_ift_loss(out, None, None, tgt, mask, 0.0, *_IFT_WEIGHTS)
+
+
 def _complex_planes(t):
     """[B, N, 2] -> the complex [B, H, W] image of its two channels (loss_functions.py:15-16)."""
     real = lin2img(t)
@@ -545,9 +713,15 @@ def kspace_l1(mask, model_output, gt):
 
 def ift_image_mse(mask, model_output, gt):
     """loss_functions.py:192-229: SSE of the magnitude images (ifft2 of the complex k-space, with the
-    optional mask), plus 1e-8 of the k-space magnitude sum, plus 0.0025 of the k-space SSE (the
-    native weighted SSE on the GPU)."""
+    optional mask), plus 1e-8 of the k-space magnitude sum, plus 0.0025 of the k-space SSE. On the
+    GPU, [B, side^2, 2] float32 with side 8 to 128 runs on siren_mri_amd::kspace_ift_loss (both
+    transforms and the three sums in one launch, the backward in one more, the data consistency of a
+    native DataConsistencyInKspace output folded in); everything else on the expression below, with
+    the native weighted SSE for its last term."""
     out, tgt = model_output["model_out"], gt["img"]
+    fused = _ift_loss_native(mask, out, tgt)
+    if fused is not None:
+        return {"img_loss": fused}
     _, kspace_output = _complex_planes(out)
     _, kspace_gt = _complex_planes(tgt)
     img_output = torch.abs(torch.fft.ifft2(kspace_output))
