@@ -122,6 +122,13 @@ int check_buffers(const void* saved, int64_t saved_bytes, int64_t saved_need, bo
   return SIREN_OK;
 }
 
+// The hand-off workspace of the loss kernels (siren_sse_workspace_bytes()): LOSS_SLOTS sums, then the
+// counter.
+void loss_workspace_slice(void* workspace, float** partial, unsigned** counter) {
+  *partial = (float*)workspace;
+  *counter = (unsigned*)((char*)workspace + LOSS_SLOTS * 4);
+}
+
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(SIREN_ELAUNCH, "%s: %s", what, hipGetErrorString(e));

@@ -3,18 +3,20 @@
 // siren_runtime.hip.
 namespace {
 
-// one launch of KERNEL<kind> (kind checked by kloss_check)
-#define KLOSS_LAUNCH(KERNEL, kind, blocks, stream, a)                                                   \
-  do {                                                                                                   \
-    switch (kind) {                                                                                      \
-      case SIREN_KLOSS_ASINH: hipLaunchKernelGGL(KERNEL<KL_ASINH>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
-      case SIREN_KLOSS_CUBIC: hipLaunchKernelGGL(KERNEL<KL_CUBIC>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
-      case SIREN_KLOSS_SMAPE: hipLaunchKernelGGL(KERNEL<KL_SMAPE>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break; \
-      case SIREN_KLOSS_L1: hipLaunchKernelGGL(KERNEL<KL_L1>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;       \
-      case SIREN_KLOSS_PERP: hipLaunchKernelGGL(KERNEL<KL_PERP>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;   \
-      default: hipLaunchKernelGGL(KERNEL<KL_LOG>, dim3(blocks), dim3(KL_THREADS), 0, stream, a); break;                  \
-    }                                                                                                    \
-  } while (0)
+// The hand-off workspace of a loss forward, checked and sliced; 0 or SIREN_EINVAL (message set).
+int loss_slots(const char* what, void* workspace, int64_t ws_bytes, float** partial, unsigned** counter) {
+  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
+    return fail(SIREN_EINVAL, "%s: workspace of %lld bytes, need %lld", what, (long long)ws_bytes,
+                (long long)siren_sse_workspace_bytes());
+  loss_workspace_slice(workspace, partial, counter);
+  return SIREN_OK;
+}
+
+// the forms of a k-space loss kernel, by SIREN_KLOSS_* (kind checked by kloss_check)
+#define SIREN_KINDS(K) \
+  {SIREN_K(K<KL_ASINH>), SIREN_K(K<KL_CUBIC>), SIREN_K(K<KL_SMAPE>), SIREN_K(K<KL_L1>), SIREN_K(K<KL_PERP>), SIREN_K(K<KL_LOG>)}
+const Kernel<KlossArgs> kKlossFwd[SIREN_KLOSS_KINDS] = SIREN_KINDS(kloss_fwd_kernel);
+const Kernel<KlossArgs> kKlossBwd[SIREN_KLOSS_KINDS] = SIREN_KINDS(kloss_bwd_kernel);
 
 // the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
 int kloss_check(const char* what, int kind, const siren_kloss_desc* desc, const float* k0, const float* mask,
@@ -22,8 +24,8 @@ int kloss_check(const char* what, int kind, const siren_kloss_desc* desc, const 
   if (kind < 0 || kind >= SIREN_KLOSS_KINDS)
     return fail(SIREN_EINVAL, "%s: kind %d outside [0, %d)", what, kind, (int)SIREN_KLOSS_KINDS);
   if (!desc) return fail(SIREN_EINVAL, "%s: null descriptor", what);
-  if (channels < 1 || channels > KL_MAXC)
-    return fail(SIREN_EINVAL, "%s: channels %d outside [1, %d]", what, channels, KL_MAXC);
+  if (channels < 1 || channels > KSPACE_MAXC)
+    return fail(SIREN_EINVAL, "%s: channels %d outside [1, %d]", what, channels, KSPACE_MAXC);
   if ((kind == SIREN_KLOSS_PERP || kind == SIREN_KLOSS_LOG) && channels != 2)
     return fail(SIREN_EINVAL, "%s: kind %d (%s) takes complex pixels, channels == 2, got %d", what, kind,
                 kind == SIREN_KLOSS_PERP ? "perp" : "log", channels);
@@ -54,17 +56,16 @@ KlossArgs kloss_args(const siren_kloss_desc* d, const float* pred, const float* 
   return a;
 }
 
-// one launch of KERNEL<log2 side>, one workgroup per slice (side checked by kfft_log2)
-#define KFFT_LAUNCH(KERNEL, lg, slices, stream, a)                                                                 \
-  do {                                                                                                             \
-    switch (lg) {                                                                                                  \
-      case 3: hipLaunchKernelGGL(KERNEL<3>, dim3(slices), dim3(KfGeom<3>::T), 0, stream, a); break;                \
-      case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(slices), dim3(KfGeom<4>::T), 0, stream, a); break;                \
-      case 5: hipLaunchKernelGGL(KERNEL<5>, dim3(slices), dim3(KfGeom<5>::T), 0, stream, a); break;                \
-      case 6: hipLaunchKernelGGL(KERNEL<6>, dim3(slices), dim3(KfGeom<6>::T), 0, stream, a); break;                \
-      default: hipLaunchKernelGGL(KERNEL<7>, dim3(slices), dim3(KfGeom<7>::T), 0, stream, a); break;               \
-    }                                                                                                              \
-  } while (0)
+// the forms of a transform kernel, by log2 side - 3 (side checked by kfft_log2); one workgroup of
+// KfGeom<log2 side>::T threads per slice
+#define SIREN_SIDES(K) {SIREN_K(K<3>), SIREN_K(K<4>), SIREN_K(K<5>), SIREN_K(K<6>), SIREN_K(K<7>)}
+const Kernel<KfftArgs> kKfft2[5] = SIREN_SIDES(kfft2_kernel);
+const Kernel<KiftArgs> kKiftFwd[5] = SIREN_SIDES(kift_fwd_kernel);
+const Kernel<KiftArgs> kKiftBwd[5] = SIREN_SIDES(kift_bwd_kernel);
+template <class Args>
+int launch_slices(const Kernel<Args> (&k)[5], int lg, int64_t slices, const char* what, void* stream, const Args& a) {
+  return launch_kernel(k[lg - 3], dim3((unsigned)slices), std::min(1u << (2 * lg), 1024u), 0, what, (hipStream_t)stream, a);
+}
 
 // log2 of a supported side (8, 16, 32, 64, 128), or -1
 int kfft_log2(int side) {
@@ -80,9 +81,9 @@ int kift_check(const char* what, const siren_kift_desc* desc, const float* pred,
   if (!desc) return fail(SIREN_EINVAL, "%s: null descriptor", what);
   if (!pred || !tgt) return fail(SIREN_EINVAL, "%s: null pointer", what);
   if ((!k0) != (!mask)) return fail(SIREN_EINVAL, "%s: k0 and mask go together (data consistency)", what);
-  if (batch < 1 || batch > KF_MAX_SLICES)
+  if (batch < 1 || batch > LOSS_SLOTS)
     return fail(SIREN_EINVAL, "%s: batch %lld outside [1, %d] (one workspace slot per slice)", what, (long long)batch,
-                KF_MAX_SLICES);
+                LOSS_SLOTS);
   if (img_mask && img_mask_bstride != 0 && img_mask_bstride != (int64_t)side * side)
     return fail(SIREN_EINVAL, "%s: img_mask batch stride %lld is neither 0 nor side^2", what,
                 (long long)img_mask_bstride);
@@ -109,29 +110,25 @@ KiftArgs kift_args(const siren_kift_desc* d, const float* pred, const float* k0,
 
 extern "C" {
 
-int64_t siren_sse_workspace_bytes(void) { return (int64_t)SSE_MAX_BLOCKS * 4 + 256; }
+int64_t siren_sse_workspace_bytes(void) { return (int64_t)LOSS_SLOTS * 4 + 256; }
 
 int siren_sse_forward(const float* pred, const float* tgt, const float* mask, int64_t n, int64_t mask_n,
                       float weight, float* d, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
   if (n < 0 || !loss || (n > 0 && (!pred || !tgt || !d)) || (mask && mask_n <= 0))
     return fail(SIREN_EINVAL, "sse_forward: bad arguments (n=%lld, mask_n=%lld)", (long long)n, (long long)mask_n);
-  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
-    return fail(SIREN_EINVAL, "sse_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
-                (long long)siren_sse_workspace_bytes());
   SseFwdArgs a;
+  if (int rc = loss_slots("sse_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
   a.pred = pred;
   a.tgt = tgt;
   a.mask = mask;
   a.d = d;
   a.loss = loss;
-  a.partial = (float*)workspace;
-  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
   a.n = n;
   a.mask_n = mask ? mask_n : 1;
   a.weight = weight;
   // 16 elements per thread: few enough blocks that the hand-off counter (one agent-scope add per
   // block, all on one address) stays off the critical path (262144 elements: 64 blocks)
-  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(SSE_MAX_BLOCKS, cdiv(n, 16 * SSE_THREADS)));
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(LOSS_SLOTS, cdiv(n, 16 * SSE_THREADS)));
   hipLaunchKernelGGL(sse_fwd_kernel, dim3(blocks), dim3(SSE_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("sse_forward");
 }
@@ -156,7 +153,7 @@ int siren_sse_backward(const float* d, const float* mask, int64_t n, int64_t mas
 
 int siren_dc_forward(const float* pred, const float* k0, const float* mask, int64_t batch, int64_t npix,
                      int channels, float noise, float* out, void* stream) {
-  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!pred || !k0 || !mask || !out)))
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KSPACE_MAXC || (batch * npix > 0 && (!pred || !k0 || !mask || !out)))
     return fail(SIREN_EINVAL, "dc_forward: bad arguments (batch=%lld, npix=%lld, channels=%d)", (long long)batch,
                 (long long)npix, channels);
   if (batch * npix == 0) return SIREN_OK;
@@ -168,7 +165,7 @@ int siren_dc_forward(const float* pred, const float* k0, const float* mask, int6
 
 int siren_dc_backward(const float* g, const float* mask, int64_t batch, int64_t npix, int channels, float noise,
                       float* dpred, void* stream) {
-  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!g || !mask || !dpred)))
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KSPACE_MAXC || (batch * npix > 0 && (!g || !mask || !dpred)))
     return fail(SIREN_EINVAL, "dc_backward: bad arguments");
   if (batch * npix == 0) return SIREN_OK;
   DcArgs a{g, nullptr, mask, dpred, batch, npix, channels, noise, 1};
@@ -180,25 +177,22 @@ int siren_dc_backward(const float* g, const float* mask, int64_t batch, int64_t 
 int siren_kspace_sse_forward(const float* pred, const float* k0, const float* mask, const float* tgt,
                              const float* hf, int64_t batch, int64_t npix, int channels, float noise, float weight,
                              float* d, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
-  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || !loss || (!k0) != (!mask) ||
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KSPACE_MAXC || !loss || (!k0) != (!mask) ||
       (batch * npix > 0 && (!pred || !tgt || !d)))
     return fail(SIREN_EINVAL, "kspace_sse_forward: bad arguments (batch=%lld, npix=%lld, channels=%d)",
                 (long long)batch, (long long)npix, channels);
-  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
-    return fail(SIREN_EINVAL, "kspace_sse_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
-                (long long)siren_sse_workspace_bytes());
-  KsseFwdArgs a{pred, k0, mask, tgt, hf, d, loss, (float*)workspace,
-                (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4), batch, npix, channels, noise, weight};
+  KsseFwdArgs a{pred, k0, mask, tgt, hf, d, loss, nullptr, nullptr, batch, npix, channels, noise, weight};
+  if (int rc = loss_slots("kspace_sse_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
   // 8 coordinates per thread: few blocks for the hand-off counter (32 x 16384 coordinates: 256)
   const unsigned blocks =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(KS_MAX_BLOCKS, cdiv(batch * npix, 8 * KS_THREADS)));
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(LOSS_SLOTS, cdiv(batch * npix, 8 * KS_THREADS)));
   hipLaunchKernelGGL(ksse_fwd_kernel, dim3(blocks), dim3(KS_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("kspace_sse_forward");
 }
 
 int siren_kspace_sse_backward(const float* d, const float* mask, const float* hf, int64_t batch, int64_t npix,
                               int channels, float noise, const float* g, float scale, float* dpred, void* stream) {
-  if (batch < 0 || npix < 0 || channels < 1 || channels > KS_MAXC || (batch * npix > 0 && (!d || !g || !dpred)))
+  if (batch < 0 || npix < 0 || channels < 1 || channels > KSPACE_MAXC || (batch * npix > 0 && (!d || !g || !dpred)))
     return fail(SIREN_EINVAL, "kspace_sse_backward: bad arguments");
   if (batch * npix == 0) return SIREN_OK;
   KsseBwdArgs a{d, mask, hf, g, dpred, batch, npix, channels, noise, scale};
@@ -212,19 +206,13 @@ int siren_kspace_loss_forward(int kind, const siren_kloss_desc* desc, const floa
                               float noise, float* loss, void* workspace, int64_t ws_bytes, void* stream) {
   if (int rc = kloss_check("kspace_loss_forward", kind, desc, k0, mask, batch, npix, channels)) return rc;
   if (!loss || (batch * npix > 0 && (!pred || !tgt))) return fail(SIREN_EINVAL, "kspace_loss_forward: null pointer");
-  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
-    return fail(SIREN_EINVAL, "kspace_loss_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
-                (long long)siren_sse_workspace_bytes());
-  static_assert(KL_MAX_BLOCKS == SSE_MAX_BLOCKS, "the hand-off's slots are siren_sse_workspace_bytes()'s");
   KlossArgs a = kloss_args(desc, pred, k0, mask, tgt, batch, npix, channels, noise);
+  if (int rc = loss_slots("kspace_loss_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
   a.out = loss;
-  a.partial = (float*)workspace;
-  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
   // 8 coordinates per thread, as kspace_sse_forward: few blocks for the hand-off counter
   const unsigned blocks =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(KL_MAX_BLOCKS, cdiv(batch * npix, 8 * KL_THREADS)));
-  KLOSS_LAUNCH(kloss_fwd_kernel, kind, blocks, (hipStream_t)stream, a);
-  return check_launch("kspace_loss_forward");
+      (unsigned)std::max<int64_t>(1, std::min<int64_t>(LOSS_SLOTS, cdiv(batch * npix, 8 * KL_THREADS)));
+  return launch_kernel(kKlossFwd[kind], dim3(blocks), KL_THREADS, 0, "kspace_loss_forward", (hipStream_t)stream, a);
 }
 
 int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const float* pred, const float* k0,
@@ -238,8 +226,7 @@ int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const flo
   a.g = g;
   a.out = dpred;
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KL_THREADS)));
-  KLOSS_LAUNCH(kloss_bwd_kernel, kind, blocks, (hipStream_t)stream, a);
-  return check_launch("kspace_loss_backward");
+  return launch_kernel(kKlossBwd[kind], dim3(blocks), KL_THREADS, 0, "kspace_loss_backward", (hipStream_t)stream, a);
 }
 
 int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream) {
@@ -250,8 +237,7 @@ int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int i
   if (batch > 0 && (!x || !out)) return fail(SIREN_EINVAL, "kspace_fft2: null pointer");
   if (batch == 0) return SIREN_OK;
   KfftArgs a{x, out, inverse ? 1 : 0};
-  KFFT_LAUNCH(kfft2_kernel, lg, (unsigned)batch, (hipStream_t)stream, a);
-  return check_launch("kspace_fft2");
+  return launch_slices(kKfft2, lg, batch, "kspace_fft2", stream, a);
 }
 
 int siren_kspace_ift_loss_forward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
@@ -262,16 +248,10 @@ int siren_kspace_ift_loss_forward(const siren_kift_desc* desc, const float* pred
                           side))
     return rc;
   if (!loss) return fail(SIREN_EINVAL, "kspace_ift_loss_forward: null pointer");
-  if (!workspace || ws_bytes < siren_sse_workspace_bytes())
-    return fail(SIREN_EINVAL, "kspace_ift_loss_forward: workspace of %lld bytes, need %lld", (long long)ws_bytes,
-                (long long)siren_sse_workspace_bytes());
-  static_assert(KF_MAX_SLICES == SSE_MAX_BLOCKS, "the hand-off's slots are siren_sse_workspace_bytes()'s");
   KiftArgs a = kift_args(desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride, noise);
+  if (int rc = loss_slots("kspace_ift_loss_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
   a.out = loss;
-  a.partial = (float*)workspace;
-  a.counter = (unsigned*)((char*)workspace + SSE_MAX_BLOCKS * 4);
-  KFFT_LAUNCH(kift_fwd_kernel, kfft_log2(side), (unsigned)batch, (hipStream_t)stream, a);
-  return check_launch("kspace_ift_loss_forward");
+  return launch_slices(kKiftFwd, kfft_log2(side), batch, "kspace_ift_loss_forward", stream, a);
 }
 
 int siren_kspace_ift_loss_backward(const siren_kift_desc* desc, const float* pred, const float* k0, const float* mask,
@@ -285,8 +265,7 @@ int siren_kspace_ift_loss_backward(const siren_kift_desc* desc, const float* pre
   KiftArgs a = kift_args(desc, pred, k0, mask, tgt, img_mask, img_mask_batch_stride, noise);
   a.g = g;
   a.out = dpred;
-  KFFT_LAUNCH(kift_bwd_kernel, kfft_log2(side), (unsigned)batch, (hipStream_t)stream, a);
-  return check_launch("kspace_ift_loss_backward");
+  return launch_slices(kKiftBwd, kfft_log2(side), batch, "kspace_ift_loss_backward", stream, a);
 }
 
 int siren_fourier_features(const float* x, const float* B, int64_t rows, int cin, int m, float* out, void* stream) {

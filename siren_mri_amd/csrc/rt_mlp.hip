@@ -289,8 +289,7 @@ void set_loss(Args& a, const siren_loss_desc& L) {
   a.ldc = L.y_dc;
   a.ldy = L.dy;
   a.lloss = L.loss;
-  a.lpart = (float*)L.loss_workspace;
-  a.lcounter = (unsigned*)((char*)L.loss_workspace + SSE_MAX_BLOCKS * 4);
+  loss_workspace_slice(L.loss_workspace, &a.lpart, &a.lcounter);
   a.lnoise = L.noise;
   a.lweight = L.weight;
 }
@@ -302,8 +301,8 @@ int launch_last_fwd(int prec, const LastFwdArgs& a, int64_t nb, hipStream_t st) 
        {SIREN_IT(last_fwd_kernel, 0, 2, true), SIREN_IT(last_fwd_kernel, 0, 8, true)}},
       {{SIREN_IT(last_fwd_kernel, 1, 2, false), SIREN_IT(last_fwd_kernel, 1, 8, false)},
        {SIREN_IT(last_fwd_kernel, 1, 2, true), SIREN_IT(last_fwd_kernel, 1, 8, true)}}};
-  // fused image loss: at most SSE_MAX_BLOCKS workgroups (the hand-off's slots)
-  const int64_t cap = a.lloss ? SSE_MAX_BLOCKS : 4096;
+  // fused image loss: at most LOSS_SLOTS workgroups
+  const int64_t cap = a.lloss ? LOSS_SLOTS : 4096;
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(a.rows_per_batch, 8),
                                                                       std::max<int64_t>(1, cap / nb)));
   return launch_kernel(k[prec][a.lloss ? 1 : 0][a.O <= 2 ? 0 : 1][it_index(a.F)], dim3(gx, (unsigned)nb), 256, 0,

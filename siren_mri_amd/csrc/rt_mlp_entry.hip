@@ -123,8 +123,8 @@ int siren_mlp_loss_check(const siren_mlp_desc* d, const siren_loss_desc* l) {
                 (long long)d->rows_per_batch);
   const Geo g = geo_of(d);
   const int64_t wgs = path == 1 ? std::min<int64_t>(cdiv(g.rows, FREG_WG_ROWS), std::max<int64_t>(1, 256 / g.nb)) * g.nb
-                                : g.nb;  // (per-layer path: at most SSE_MAX_BLOCKS / nb workgroups per weight set)
-  if (wgs > SSE_MAX_BLOCKS) return fail(SIREN_EINVAL, "fused loss: %lld workgroups > %d", (long long)wgs, SSE_MAX_BLOCKS);
+                                : g.nb;  // (per-layer path: at most LOSS_SLOTS / nb workgroups per weight set)
+  if (wgs > LOSS_SLOTS) return fail(SIREN_EINVAL, "fused loss: %lld workgroups > %d", (long long)wgs, LOSS_SLOTS);
   return SIREN_OK;
 }
 

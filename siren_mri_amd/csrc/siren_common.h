@@ -204,6 +204,72 @@ DEV float wave_sum(float v) {
   return v;
 }
 
+// Slots of the loss kernels' hand-off workspace (siren_sse_workspace_bytes(): LOSS_SLOTS block sums,
+// then the counter), so also the most workgroups a kernel that hands off may be launched with; and
+// the most channels per coordinate of the k-space kernels.
+constexpr int LOSS_SLOTS = 1024;
+constexpr int KSPACE_MAXC = 8;
+
+// Hand-off of a deterministic sum between workgroups: every workgroup publishes its sum to a slot of
+// its own, and the last one to finish adds the slots in index order, so the result does not depend
+// on scheduling (MI355X_MICROARCH.md, "Valid forms", the first row of the table of hand-offs measured
+// with sc1 loads in place of the acquire). Every atomic below is RELAXED at agent scope; the ordering
+// comes from the hardware path, not from the C++ memory model:
+//   producer: one lane per workgroup stores its sum write-through (relaxed agent-scope store =
+//             global_store sc1), drains it with an explicit s_waitcnt vmcnt(0) (inline asm, so the
+//             compiler cannot drop it), then takes a ticket with one agent-scope atomic add;
+//   consumer: the workgroup whose add returned the workgroup count - 1 reads every sum with sc1
+//             loads (relaxed agent-scope loads = global_load sc1, served from L2, never from a stale
+//             L1), then stores 0 to the counter: it is zero between launches.
+// This avoids the L2 write-back / invalidate of acq_rel fences (several us per launch). The
+// slots/counter workspace is per (device, stream) on the host side, so two launches never share it
+// concurrently.
+DEV unsigned handoff_publish(float* slot, float s, unsigned* counter) {
+  __hip_atomic_store(slot, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV float handoff_read(const float* slot) {
+  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV void handoff_rearm(unsigned* counter) {
+  __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The whole of it for a workgroup of WAVES waves (every thread calls it, with its own sum): the wave
+// sums, the waves in index order, published to slot wg of nwg; in the last workgroup thread t adds
+// slots t, t + 64 WAVES, ... in order, then the same tree, and out[0] = total * weight.
+template <int WAVES>
+DEV void block_sum_handoff(float acc, float* partial, unsigned* counter, unsigned wg, unsigned nwg, float* out,
+                           float weight) {
+  __shared__ float red[WAVES];
+  __shared__ unsigned ticket;
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) s += red[w];
+    ticket = handoff_publish(partial + wg, s, counter);
+  }
+  __syncthreads();
+  if (ticket != nwg - 1) return;
+  float s = 0.f;
+  for (unsigned b = threadIdx.x; b < nwg; b += WAVES * 64) s += handoff_read(partial + b);
+  s = wave_sum(s);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) tot += red[w];
+    out[0] = tot * weight;
+    handoff_rearm(counter);
+  }
+}
+
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // ds_read_b64_tr_b16: lane (4q+p) of each 16-lane group supplies the address of row q,

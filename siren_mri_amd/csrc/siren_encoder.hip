@@ -94,9 +94,8 @@ DEV void enc_block_sum(const EncArgs& a, const float (&acc)[8], int c0, int pix,
     for (int r = 0; r < ppi; ++r) s += red[r * nc + c];
     __hip_atomic_store(a.part + (int64_t)blk * nc + c, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  // hand-off without an L2 write-back (siren_loss.hip, sse_fwd_kernel): write-through (relaxed
-  // agent-scope = sc1) stores of the block's row drained by every writing lane, a barrier, then one
-  // relaxed agent-scope ticket; the last block reads the rows with sc1 loads
+  // the hand-off of siren_common.h with a row per block, published by many lanes: every writing lane
+  // drains its write-through stores, a barrier, then the one ticket
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __shared__ unsigned last;
   __syncthreads();
@@ -106,25 +105,24 @@ DEV void enc_block_sum(const EncArgs& a, const float (&acc)[8], int c0, int pix,
   // The rows are read 32 loads at a time before any is added (a chain of single sc1 loads made
   // this tail 0.2-0.5 ms; 8 at a time still left 64 load latencies in a row for 1,024 blocks), in a
   // fixed order: deterministic.
-  auto ld = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   auto sum_rows = [&](const float* src, unsigned b0, unsigned b1, int64_t stride) {
     float s = 0.f;
     unsigned b = b0;
     for (; b + 32 <= b1; b += 32) {
       float v[32];
 #pragma unroll
-      for (int k = 0; k < 32; ++k) v[k] = ld(src + (int64_t)(b + k) * stride);
+      for (int k = 0; k < 32; ++k) v[k] = handoff_read(src + (int64_t)(b + k) * stride);
 #pragma unroll
       for (int k = 0; k < 32; ++k) s += v[k];
     }
     for (; b + 8 <= b1; b += 8) {
       float v[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = ld(src + (int64_t)(b + k) * stride);
+      for (int k = 0; k < 8; ++k) v[k] = handoff_read(src + (int64_t)(b + k) * stride);
 #pragma unroll
       for (int k = 0; k < 8; ++k) s += v[k];
     }
-    for (; b < b1; ++b) s += ld(src + (int64_t)b * stride);
+    for (; b < b1; ++b) s += handoff_read(src + (int64_t)b * stride);
     return s;
   };
   if (ncol == nc) {
@@ -149,7 +147,7 @@ DEV void enc_block_sum(const EncArgs& a, const float (&acc)[8], int c0, int pix,
       dst[k] = addend ? s + *addend : s;
     }
   }
-  if (tid == 0) __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) handoff_rearm(a.ticket);
 }
 
 // g = (g1 [+ g2]) * (y > 0) -> out; db = channel sums of g (as stored, bf16-rounded)
@@ -467,8 +465,7 @@ __global__ __launch_bounds__(256) void sumsq_fwd_kernel(SumsqArgs a) {
   if (!last) return;
   // the last block: thread t adds partials t, t + 256, ... in order, then the same LDS tree
   float s = 0.f;
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += 256)
-    s += __hip_atomic_load(a.part + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) s += handoff_read(a.part + b);
   red[threadIdx.x] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
@@ -477,7 +474,7 @@ __global__ __launch_bounds__(256) void sumsq_fwd_kernel(SumsqArgs a) {
   }
   if (threadIdx.x == 0) {
     *a.out = red[0];
-    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    handoff_rearm(a.counter);
   }
 }
 __global__ __launch_bounds__(256) void sumsq_bwd_kernel(SumsqArgs a) {

@@ -872,8 +872,7 @@ __global__ __launch_bounds__(512) void fused_fwd_reg_kernel(FwdRegArgs a) {
   // no LDS-DMA may land after the workgroup has released its LDS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (LOSS) {
-    // workgroup sum (waves in order), then the last workgroup to finish adds the workgroup sums in
-    // index order (the hand-off of siren_loss.hip / siren_kspace.hip)
+    // block_sum_handoff<8> (siren_common.h) written out: calling it re-allocates the whole kernel's registers
     __shared__ float lred[8];
     __shared__ unsigned lticket;
     const float ws_ = wave_sum(lsum);

@@ -24,15 +24,13 @@
 // The loss forward is one launch: transform t and keep |x_t| in registers (the thread that owns a
 // pixel owns it in both transforms), load y into the tile while summing the two k-space terms,
 // transform y, sum the image term; a fixed tree per slice, and the last workgroup adds the slice sums
-// in slice order (the hand-off of kl_handoff, one slot per slice). The backward is one launch that
+// in slice order (the hand-off of siren_common.h, one slot per slice). The backward is one launch that
 // recomputes everything from pred and tgt: g_x = 2 w m (|x_y| - |x_t|) x_y / |x_y| (0 at |x_y| = 0,
 // torch's gradient of a complex magnitude), the forward transform of g_x over side^2 (the adjoint of
 // ifft2), plus the k-space terms' gradients, times the upstream gradient and the DC's coefficient.
 #include "siren_common.h"
 
 namespace siren {
-
-constexpr int KF_MAX_SLICES = 1024;  // the hand-off's slots (SSE_MAX_BLOCKS): one per slice
 
 template <int L>
 struct KfGeom {
@@ -64,7 +62,7 @@ struct KiftArgs {
   const float* img_mask;  // [N] or [B, N] (null: none)
   const float* g;         // [1] upstream gradient of the loss (backward)
   float* out;             // forward: [1] the loss; backward: [B, N, 2] dL / dpred
-  float* partial;         // [KF_MAX_SLICES] per-slice sums (workspace, forward)
+  float* partial;         // [LOSS_SLOTS] per-slice sums (workspace, forward)
   unsigned* counter;      // zero between launches (the last workgroup resets it)
   int64_t img_mask_bstride;  // 0 or N
   float noise;
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(KfGeom<L>::T) void kift_fwd_kernel(KiftArgs a) {
   using G = KfGeom<L>;
   __shared__ KfTile<L> t;
   __shared__ float red[16];
-  __shared__ float slots[KF_MAX_SLICES];
+  __shared__ float slots[LOSS_SLOTS];
   __shared__ unsigned ticket;
   const int64_t slice = blockIdx.x;
   const float inv_n = 1.f / (float)G::N;
@@ -255,21 +253,18 @@ __global__ __launch_bounds__(KfGeom<L>::T) void kift_fwd_kernel(KiftArgs a) {
     float s = 0.f;
 #pragma unroll
     for (int w = 0; w < (G::T + 63) / 64; ++w) s += red[w];
-    __hip_atomic_store(a.partial + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ticket = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket = handoff_publish(a.partial + blockIdx.x, s, a.counter);
   }
   __syncthreads();
   if (ticket != gridDim.x - 1) return;
   // the last workgroup: the slice sums in slice order
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += G::T)
-    slots[b] = __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += G::T) slots[b] = handoff_read(a.partial + b);
   __syncthreads();
   if (threadIdx.x == 0) {
     float tot = 0.f;
     for (unsigned b = 0; b < gridDim.x; ++b) tot = __fadd_rn(tot, slots[b]);
     a.out[0] = tot;
-    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    handoff_rearm(a.counter);
   }
 }
 

@@ -13,7 +13,7 @@
 //   log    w sum_pixels wm (log(|y| + eps) - log(|t| + eps))^2
 //                       + wp (2 - cos(arg y - arg t))                image_mse_log     C == 2
 //
-// The forward is one launch (the deterministic sum and hand-off of ksse_fwd_kernel); the backward is
+// The forward is one launch (the deterministic sum of block_sum_handoff); the backward is
 // one launch that recomputes dL/dy from pred and tgt, so nothing is saved between the two. The zero
 // cases follow torch's autograd, which the reference runs on: sign(0) = 0, d|x|/dx = 0 at 0, the
 // gradients of a complex magnitude and of a complex angle are 0 at 0, arg 0 = 0. Differences that
@@ -25,8 +25,6 @@
 namespace siren {
 
 constexpr int KL_THREADS = 256;
-constexpr int KL_MAX_BLOCKS = 1024;  // the hand-off's slots (SSE_MAX_BLOCKS)
-constexpr int KL_MAXC = 8;  // channels (KS_MAXC)
 
 enum { KL_ASINH = 0, KL_CUBIC = 1, KL_SMAPE = 2, KL_L1 = 3, KL_PERP = 4, KL_LOG = 5 };
 
@@ -37,7 +35,7 @@ struct KlossArgs {
   const float* tgt;    // [B, N, C]
   const float* g;      // [1] upstream gradient of the loss (backward)
   float* out;          // forward: [1] the loss; backward: [B, N, C] dL / dpred
-  float* partial;      // [KL_MAX_BLOCKS] per-block sums (workspace, forward)
+  float* partial;      // [LOSS_SLOTS] per-block sums (workspace, forward)
   unsigned* counter;   // zero between launches (the last block resets it)
   int64_t batch, npix;
   int C;
@@ -153,40 +151,7 @@ DEV float kl_y(const KlossArgs& a, int64_t q, int64_t b, int64_t n, int c) {
   return dc_value(v, a.k0[pl], a.mask[pl], a.noise);
 }
 
-// Per-thread sums over a fixed grid-stride order, a fixed block tree, and the last block adds the
-// block sums in index order: the hand-off of ksse_fwd_kernel (siren_kspace.hip), for these kernels.
-DEV void kl_handoff(float acc, float* partial, unsigned* counter, float* loss, float weight) {
-  __shared__ float red[KL_THREADS / 64];
-  __shared__ unsigned ticket;
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < KL_THREADS / 64; ++w) s += red[w];
-    __hip_atomic_store(partial + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (ticket != gridDim.x - 1) return;
-  float s = 0.f;
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += KL_THREADS)
-    s += __hip_atomic_load(partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  s = wave_sum(s);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < KL_THREADS / 64; ++w) tot += red[w];
-    loss[0] = tot * weight;
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
+// Per-thread sums over a fixed grid-stride order, then block_sum_handoff (siren_common.h).
 template <int KIND>
 __global__ __launch_bounds__(KL_THREADS) void kloss_fwd_kernel(KlossArgs a) {
   float acc = 0.f;
@@ -203,7 +168,7 @@ __global__ __launch_bounds__(KL_THREADS) void kloss_fwd_kernel(KlossArgs a) {
         acc = __fadd_rn(acc, kl_chan_value<KIND>(a, kl_y(a, q, b, n, c), a.tgt[q * a.C + c]));
     }
   }
-  kl_handoff(acc, a.partial, a.counter, a.out, a.weight);
+  block_sum_handoff<KL_THREADS / 64>(acc, a.partial, a.counter, blockIdx.x, gridDim.x, a.out, a.weight);
 }
 
 // dL/dpred = g w dL/dy dc_coef(mask)

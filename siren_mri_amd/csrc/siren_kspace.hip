@@ -18,8 +18,6 @@
 namespace siren {
 
 constexpr int KS_THREADS = 256;
-constexpr int KS_MAX_BLOCKS = 1024;
-constexpr int KS_MAXC = 8;
 
 struct DcArgs {
   const float* pred;   // [B, N, C] forward input / backward upstream gradient
@@ -53,18 +51,15 @@ struct KsseFwdArgs {
   const float* hf;     // [N] (null: no mask)
   float* d;            // [B, N, C] hf (DC(pred) - tgt), kept for the backward
   float* loss;         // [1]
-  float* partial;      // [KS_MAX_BLOCKS] per-block sums (workspace)
+  float* partial;      // [LOSS_SLOTS] per-block sums (workspace)
   unsigned* counter;   // zero between launches (the last block resets it)
   int64_t batch, npix;
   int C;
   float noise, weight;
 };
 
-// Per-thread sums over a fixed grid-stride order, a fixed block tree, and the last block adds the
-// block sums in index order (the hand-off of sse_fwd_kernel, siren_loss.hip): deterministic.
+// Per-thread sums over a fixed grid-stride order, then block_sum_handoff (siren_common.h): deterministic.
 __global__ __launch_bounds__(KS_THREADS) void ksse_fwd_kernel(KsseFwdArgs a) {
-  __shared__ float red[KS_THREADS / 64];
-  __shared__ unsigned ticket;
   float acc = 0.f;
   const int64_t nq = a.batch * a.npix;
   const int64_t stride = (int64_t)gridDim.x * KS_THREADS;
@@ -83,33 +78,7 @@ __global__ __launch_bounds__(KS_THREADS) void ksse_fwd_kernel(KsseFwdArgs a) {
       acc = fmaf(dd, dd, acc);
     }
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < KS_THREADS / 64; ++w) s += red[w];
-    __hip_atomic_store(a.partial + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ticket = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (ticket != gridDim.x - 1) return;
-  float s = 0.f;
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += KS_THREADS)
-    s += __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  s = wave_sum(s);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < KS_THREADS / 64; ++w) tot += red[w];
-    a.loss[0] = tot * a.weight;
-    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  block_sum_handoff<KS_THREADS / 64>(acc, a.partial, a.counter, blockIdx.x, gridDim.x, a.loss, a.weight);
 }
 
 struct KsseBwdArgs {

@@ -9,7 +9,6 @@
 namespace siren {
 
 constexpr int SSE_THREADS = 256;
-constexpr int SSE_MAX_BLOCKS = 1024;
 
 struct SseFwdArgs {
   const float* pred;
@@ -17,29 +16,15 @@ struct SseFwdArgs {
   const float* mask;   // null: no mask
   float* d;            // [n] m (pred - tgt), kept for the backward
   float* loss;         // [1]
-  float* partial;      // [SSE_MAX_BLOCKS] per-block sums (workspace)
+  float* partial;      // [LOSS_SLOTS] per-block sums (workspace)
   unsigned* counter;   // zero between launches (the last block resets it)
   int64_t n, mask_n;
   float weight;
 };
 
-// Per-thread sums over a fixed grid-stride order, a fixed-order block tree, and the last block
-// to finish adds the block sums in index order: the result does not depend on scheduling.
-//
-// Hand-off of the block sums (MI355X_MICROARCH.md, "Valid forms", the first row of the table of
-// hand-offs measured with sc1 loads in place of the acquire). Every atomic below is RELAXED at
-// agent scope; the ordering comes from the hardware path, not from the C++ memory model:
-//   producer: one lane per block stores its sum write-through (relaxed agent-scope store =
-//             global_store sc1), drains it with an explicit s_waitcnt vmcnt(0) (inline asm, so the
-//             compiler cannot drop it), then takes a ticket with one agent-scope atomic add;
-//   consumer: the block whose add returned gridDim.x - 1 reads every sum with sc1 loads (relaxed
-//             agent-scope loads = global_load sc1, served from L2, never from a stale L1).
-// This avoids the L2 write-back / invalidate of acq_rel fences (several us per launch). The
-// partial/counter workspace is per (device, stream) on the host side, so two launches never share
-// it concurrently.
+// Per-thread sums over a fixed grid-stride order, then block_sum_handoff (siren_common.h): the result
+// does not depend on scheduling.
 __global__ __launch_bounds__(SSE_THREADS) void sse_fwd_kernel(SseFwdArgs a) {
-  __shared__ float red[SSE_THREADS / 64];
-  __shared__ unsigned ticket;
   float acc = 0.f;
   const int64_t stride = (int64_t)gridDim.x * SSE_THREADS;
   const int64_t tid0 = (int64_t)blockIdx.x * SSE_THREADS + threadIdx.x;
@@ -60,37 +45,7 @@ __global__ __launch_bounds__(SSE_THREADS) void sse_fwd_kernel(SseFwdArgs a) {
     a.d[e] = v;
     acc = fmaf(v, v, acc);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < SSE_THREADS / 64; ++w) s += red[w];
-    // hand-off without an L2 write-back (MI355X_MICROARCH.md, inter-workgroup visibility, first
-    // form): write-through (sc1) store of the block sum, drained, then one agent-scope add; the
-    // block whose add comes last reads every sum with sc1 loads
-    __hip_atomic_store(a.partial + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ticket = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (ticket != gridDim.x - 1) return;
-  // last block: thread t adds block sums t, t + 256, ... in order, then the same fixed tree
-  float s = 0.f;
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += SSE_THREADS)
-    s += __hip_atomic_load(a.partial + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  s = wave_sum(s);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < SSE_THREADS / 64; ++w) tot += red[w];
-    a.loss[0] = tot * a.weight;
-    __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  block_sum_handoff<SSE_THREADS / 64>(acc, a.partial, a.counter, blockIdx.x, gridDim.x, a.loss, a.weight);
 }
 
 struct SseBwdArgs {

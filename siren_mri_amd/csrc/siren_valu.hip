@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void first_fwd_kernel(FirstFwdArgs a) {
 // LOSS: also the fused image loss (siren_mlp_forward_loss on the per-layer path: fp32 mode and the
 // bf16 shapes outside the register forward): per output element p = DC(y) (with k0), d = hf (p - t),
 // the lane's sum of d^2, DC(y) and dL/dy = 2 w hf d dDC/dy — fused_fwd_reg_kernel's LOSS epilogue
-// arithmetic — then the workgroup sums through the write-through ticket hand-off of siren_loss.hip
+// arithmetic — then the workgroup sums through the write-through ticket hand-off of siren_common.h
 // (deterministic: fixed per-lane row order, wave / workgroup trees, workgroup sums in index order).
 template <int PREC, int IT, int MAXO, bool LOSS = false>
 __global__ __launch_bounds__(256) void last_fwd_kernel(LastFwdArgs a) {
@@ -272,22 +272,20 @@ __global__ __launch_bounds__(256) void last_fwd_kernel(LastFwdArgs a) {
     __syncthreads();
     const unsigned nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
     if (tid == 0) {
-      const float sacc = (lred[0] + lred[1]) + (lred[2] + lred[3]);
-      __hip_atomic_store(a.lpart + wg, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      lticket = __hip_atomic_fetch_add(a.lcounter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // (the waves pairwise, not in index order as block_sum_handoff adds them)
+      lticket = handoff_publish(a.lpart + wg, (lred[0] + lred[1]) + (lred[2] + lred[3]), a.lcounter);
     }
     __syncthreads();
     if (lticket == nwg - 1) {
       float sacc = 0.f;
-      for (unsigned b = tid; b < nwg; b += 256) sacc += __hip_atomic_load(a.lpart + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (unsigned b = tid; b < nwg; b += 256) sacc += handoff_read(a.lpart + b);
       sacc = wave_sum(sacc);
       __syncthreads();
       if (lane == 0) lred[wave] = sacc;
       __syncthreads();
       if (tid == 0) {
         a.lloss[0] = ((lred[0] + lred[1]) + (lred[2] + lred[3])) * a.lweight;
-        __hip_atomic_store(a.lcounter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        handoff_rearm(a.lcounter);
       }
     }
   }

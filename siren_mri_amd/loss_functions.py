@@ -17,7 +17,9 @@ DataConsistencyInKspace output folded in. The six k-spa
 family run on siren_mri_amd::kspace_loss (siren_kloss.hip: one forward and one backward launch, the
 DC folded in the same way); ift_image_mse runs on siren_mri_amd::kspace_ift_loss (siren_kfft.hip: the
 two ifft2 and the three sums in one forward launch, one backward launch) for square slices of side
-8 to 128, and is a PyTorch composition otherwise, as image_l1 is.
+8 to 128, and is a PyTorch composition otherwise, as image_l1 is. This module holds the reference's
+expressions, the switches and the decision which native op applies; the ops themselves and the
+autograd functions on the kernels are bound in loss_ops.py.
 
 Deliberate deviation (bug 0.2): the reference builds its high-frequency mask
 on a fixed 128x128 grid, so image_mse(high_freq=True) raises for any other image size; here the
@@ -33,6 +35,8 @@ import torch
 from . import _native, diff_operators, fusion
 from .data_consistency import dc_source
 from .dataio import lin2img
+# the native kernels' autograd functions and custom ops (importing it registers the ops)
+from .loss_ops import _kfft_side, _kift_max_batch, _SumSquares, _WeightedSSE  # noqa: F401
 from .utils import create_circular_mask_torch
 
 _KSPACE_WEIGHT = 1.0 / (128 * 128)
@@ -50,118 +54,6 @@ def _high_freq_mask(device):
         _MASKS[device] = m
     return m
 
-
-def _sse_workspace(device):
-    # one workspace per (device, stream): its block sums and ticket must not be shared by two
-    # launches that may run concurrently
-    return _native.sse_workspace(device)
-
-
-class _WeightedSSE(torch.autograd.Function):
-    """sum((m * (pred - tgt))^2) * w for real pred and a constant target on the native kernels
-    (siren_sse_forward / siren_sse_backward, siren_loss.hip): forward = one launch (d = m (pred -
-    tgt) and the deterministic weighted sum), backward = one launch, 2 w m^2 (pred - tgt) g — the
-    values of the autograd chain of (diff.abs() ** 2).sum() * w in 2 launches instead of ~6."""
-
-    @staticmethod
-    def forward(ctx, pred, tgt, mask, weight):
-        predc, tgtc = pred.contiguous(), tgt.contiguous()
-        maskc = mask.contiguous() if mask is not None else None
-        n = predc.numel()
-        d = torch.empty_like(predc)
-        loss = torch.empty((), dtype=torch.float32, device=pred.device)
-        ws = _sse_workspace(pred.device)
-        rc = _native.lib().siren_sse_forward(
-            predc.data_ptr(), tgtc.data_ptr(), maskc.data_ptr() if maskc is not None else None, n,
-            maskc.numel() if maskc is not None else 0, float(weight), d.data_ptr(), loss.data_ptr(),
-            ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
-        _native.check(rc, "siren_sse_forward")
-        ctx.save_for_backward(d, maskc)
-        ctx.weight = weight
-        ctx.shape = pred.shape
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        d, mask = ctx.saved_tensors
-        gc = g.contiguous().to(torch.float32)
-        out = torch.empty_like(d)
-        rc = _native.lib().siren_sse_backward(
-            d.data_ptr(), mask.data_ptr() if mask is not None else None, d.numel(),
-            mask.numel() if mask is not None else 0, gc.data_ptr(), float(2.0 * ctx.weight), out.data_ptr(),
-            _native.stream_handle(d.device))
-        _native.check(rc, "siren_sse_backward")
-        return out.view(ctx.shape), None, None, None
-
-
-# image_mse on the SIREN output layout [B, N, C], optionally with data consistency folded in
-# (siren_kspace.hip): siren_mri_amd::kspace_sse(pred, k0?, mask?, tgt, hf?, noise, weight) -> (loss, d)
-from .ops import _LIB  # noqa: E402
-
-_LIB.define("kspace_sse(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? hf, float noise, float weight) "
-            "-> (Tensor, Tensor)")
-_LIB.define("kspace_sse_bwd(Tensor d, Tensor? mask, Tensor? hf, Tensor g, float noise, float scale) -> Tensor")
-
-
-def _kspace_sse_cuda(pred, k0, mask, tgt, hf, noise, weight):
-    b, n, c = pred.shape
-    pc, tc = pred.contiguous(), tgt.contiguous()
-    kc = k0.contiguous() if k0 is not None else None
-    mc = mask.contiguous() if mask is not None else None
-    hc = hf.contiguous() if hf is not None else None
-    d = torch.empty_like(pc)
-    loss = torch.empty((), dtype=torch.float32, device=pred.device)
-    ws = _sse_workspace(pred.device)
-    rc = _native.lib().siren_kspace_sse_forward(
-        pc.data_ptr(), kc.data_ptr() if kc is not None else None, mc.data_ptr() if mc is not None else None,
-        tc.data_ptr(), hc.data_ptr() if hc is not None else None, b, n, c, float(noise), float(weight), d.data_ptr(),
-        loss.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
-    _native.check(rc, "siren_kspace_sse_forward")
-    return loss, d
-
-
-def _kspace_sse_bwd_cuda(d, mask, hf, g, noise, scale):
-    b, n, c = d.shape
-    out = torch.empty_like(d)
-    mc = mask.contiguous() if mask is not None else None
-    hc = hf.contiguous() if hf is not None else None
-    gc = g.contiguous().to(torch.float32)
-    rc = _native.lib().siren_kspace_sse_backward(d.data_ptr(), mc.data_ptr() if mc is not None else None,
-                                                 hc.data_ptr() if hc is not None else None, b, n, c, float(noise),
-                                                 gc.data_ptr(), float(scale), out.data_ptr(),
-                                                 _native.stream_handle(d.device))
-    _native.check(rc, "siren_kspace_sse_backward")
-    return out
-
-
-class _KspaceSSEAutograd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, k0, mask, tgt, hf, noise, weight):
-        with torch._C._AutoDispatchBelowAutograd():
-            loss, d = torch.ops.siren_mri_amd.kspace_sse(pred, k0, mask, tgt, hf, noise, weight)
-        ctx.save_for_backward(d, mask, hf)
-        ctx.noise, ctx.weight = noise, weight
-        ctx.mark_non_differentiable(d)
-        ctx.set_materialize_grads(False)
-        return loss, d
-
-    @staticmethod
-    def backward(ctx, g, _gd):
-        if g is None:
-            return (None,) * 7
-        d, mask, hf = ctx.saved_tensors
-        dpred = torch.ops.siren_mri_amd.kspace_sse_bwd(d, mask, hf, g, ctx.noise, 2.0 * ctx.weight)
-        return dpred, None, None, None, None, None, None
-
-
-_LIB.impl("kspace_sse", _kspace_sse_cuda, "CUDA")
-_LIB.impl("kspace_sse_bwd", _kspace_sse_bwd_cuda, "CUDA")
-_LIB.impl("kspace_sse", lambda pred, k0, mask, tgt, hf, noise, weight:
-          _KspaceSSEAutograd.apply(pred, k0, mask, tgt, hf, noise, weight), "Autograd")
-torch.library.register_fake("siren_mri_amd::kspace_sse", lambda pred, k0, mask, tgt, hf, noise, weight:
-                            (pred.new_empty(()), torch.empty_like(pred)), lib=_LIB)
-torch.library.register_fake("siren_mri_amd::kspace_sse_bwd", lambda d, mask, hf, g, noise, scale: torch.empty_like(d),
-                            lib=_LIB)
 
 _FUSE_DC = True
 
@@ -200,22 +92,33 @@ def _hf_flat(device):
     return m
 
 
+def _native_operands(out, tgt):
+    """What every native k-space loss op takes: a float32 [B, N, C] prediction on the GPU and a target of
+    its shape on its device that needs no gradient."""
+    return (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and tgt.shape == out.shape
+            and tgt.dtype == torch.float32 and tgt.device == out.device and not tgt.requires_grad)
+
+
+def _fold_dc(out):
+    """(pred, k0, mask, noise) of a native DataConsistencyInKspace output, whose DC the loss ops then
+    compute themselves; (out, None, None, 0.0) for anything else or with set_kspace_fusion(False)."""
+    src = dc_source(out) if _FUSE_DC else None
+    if src is not None and src[0].shape == out.shape:
+        return src
+    return out, None, None, 0.0
+
+
 def _kspace_image_mse(out, tgt, high_freq):
     """image_mse on [B, N, C] (N a square): the native k-space op, or None when not applicable."""
-    if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and tgt.shape == out.shape
-            and tgt.dtype == torch.float32 and tgt.device == out.device and not tgt.requires_grad
-            and out.shape[-1] <= 8):
+    if not (_native_operands(out, tgt) and out.shape[-1] <= 8):
         return None
     n = out.shape[1]
     side = int(round(n ** 0.5))
     if side * side != n:
         return None
     hf = _hf_flat(out.device) if (high_freq and side == 128) else None
-    src = dc_source(out) if _FUSE_DC else None
-    if src is not None and src[0].shape == out.shape:
-        pred, k0, mask, noise = src
-        return torch.ops.siren_mri_amd.kspace_sse(pred, k0, mask, tgt, hf, noise, _KSPACE_WEIGHT)[0]
-    return torch.ops.siren_mri_amd.kspace_sse(out, None, None, tgt, hf, 0.0, _KSPACE_WEIGHT)[0]
+    pred, k0, mask, noise = _fold_dc(out)
+    return torch.ops.siren_mri_amd.kspace_sse(pred, k0, mask, tgt, hf, noise, _KSPACE_WEIGHT)[0]
 
 
 def weighted_sse(pred, tgt, weight=_KSPACE_WEIGHT, mask=None):
@@ -265,55 +168,6 @@ def latent_loss(model_output):
     return torch.mean(model_output["latent_vec"] ** 2)
 
 
-_SUMSQ_WS = {}
-
-
-def _sumsq_workspace(device, total):
-    """Per-(device, stream) zeroed workspace of siren_sumsq_forward (left zeroed by every launch)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
-    need = int(_native.lib().siren_sumsq_workspace_bytes(total))
-    ws = _SUMSQ_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.zeros(need, dtype=torch.uint8, device=device)
-        _SUMSQ_WS[key] = ws
-    return ws
-
-
-class _SumSquares(torch.autograd.Function):
-    """sum over tensors of torch.sum(w ** 2) in one native launch (siren_sumsq_forward), its
-    gradient 2 g w in one more (siren_sumsq_backward)."""
-
-    @staticmethod
-    def forward(ctx, *ws):
-        import ctypes
-        ts = [w.detach().contiguous() for w in ws]
-        n = len(ts)
-        numel = (ctypes.c_int64 * n)(*[t.numel() for t in ts])
-        out = torch.empty((), dtype=torch.float32, device=ts[0].device)
-        work = _sumsq_workspace(ts[0].device, sum(t.numel() for t in ts))
-        _native.check(_native.lib().siren_sumsq_forward(n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]), numel,
-                                                        out.data_ptr(), work.data_ptr(), work.numel(),
-                                                        _native.stream_handle(ts[0].device)), "siren_sumsq_forward")
-        ctx.save_for_backward(*ws)  # the inputs: a create_graph backward differentiates through them
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        import ctypes
-        if torch.is_grad_enabled():
-            # create_graph=True: the exact gradient 2 g w in differentiable PyTorch (ADVICE r5)
-            return tuple(2 * g * w if need else None for w, need in zip(ctx.saved_tensors, ctx.needs_input_grad))
-        ts = [w.detach().contiguous() for w in ctx.saved_tensors]
-        n = len(ts)
-        gc = g.detach().reshape(()).to(torch.float32).contiguous()
-        outs = [torch.empty_like(t) for t in ts]
-        _native.check(_native.lib().siren_sumsq_backward(n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]),
-                                                         (ctypes.c_int64 * n)(*[t.numel() for t in ts]), gc.data_ptr(),
-                                                         (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]),
-                                                         _native.stream_handle(ts[0].device)), "siren_sumsq_backward")
-        return tuple(o if need else None for o, need in zip(outs, ctx.needs_input_grad))
-
-
 def hypo_weight_loss(model_output):
     """loss_functions.py:279-287: the mean of the squared hypo-parameters; on CUDA fp32 the sum of
     squares is one native launch (and its gradient one more)."""
@@ -334,113 +188,6 @@ def image_hypernetwork_loss(mask, kl, fw, model_output, gt):
             "hypo_weight_loss": fw * hypo_weight_loss(model_output)}
 
 
-# The k-space loss family on the SIREN output layout [B, N, C], optionally with data consistency
-# folded in (siren_kloss.hip):
-#   siren_mri_amd::kspace_loss(pred, k0?, mask?, tgt, kind, noise) -> loss
-#   siren_mri_amd::kspace_loss_bwd(pred, k0?, mask?, tgt, g, kind, noise) -> dpred
-# The backward recomputes dL/dy from its inputs: the forward saves no residual tensor.
-_LIB.define("kspace_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, int kind, float noise) -> Tensor")
-_LIB.define("kspace_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor g, int kind, float noise) "
-            "-> Tensor")
-
-
-def _kloss_desc(weight=1.0, eps=0.0, scale=0.0, divisor=1.0, mag_weight=0.0, phase_weight=0.0):
-    return _native.SirenKlossDesc(weight, eps, scale, divisor, mag_weight, phase_weight)
-
-
-# the reference's constants, per kind (loss_functions.py:25-35, 52-57, 110-111, 127-135, 156-161, 183)
-_KLOSS_DESCS = {
-    _native.KLOSS_ASINH: _kloss_desc(weight=1 / (128 * 128), scale=400.0, divisor=6.7),
-    _native.KLOSS_CUBIC: _kloss_desc(weight=0.000001, eps=1e-3),
-    _native.KLOSS_SMAPE: _kloss_desc(weight=1 / (128 * 128), eps=1e-3),
-    _native.KLOSS_L1: _kloss_desc(weight=1 / (128 * 128)),
-    _native.KLOSS_PERP: _kloss_desc(weight=1 / (128 * 128) * 1000, eps=1e-8),
-    _native.KLOSS_LOG: _kloss_desc(weight=1.0, eps=1e-3, mag_weight=0.0001, phase_weight=0.0001),
-}
-
-
-def _kloss_desc_ref(kind):
-    import ctypes
-    desc = _KLOSS_DESCS.get(int(kind))
-    # an unknown kind goes to the library with some descriptor: its argument check reports it
-    return ctypes.byref(desc if desc is not None else _KLOSS_DESCS[_native.KLOSS_L1])
-
-
-def _kloss_operands(pred, k0, mask, tgt):
-    """Contiguous fp32 operands of the two ops, shapes checked (the kernels index by pred's shape)."""
-    if pred.dim() != 3 or tgt.shape != pred.shape:
-        raise RuntimeError(f"siren_mri_amd.kspace_loss: pred {tuple(pred.shape)} must be [B, N, C] and tgt "
-                           f"{tuple(tgt.shape)} of the same shape")
-    b, n, c = pred.shape
-    for name, t in (("k0", k0), ("mask", mask)):
-        if t is not None and (t.dim() < 3 or t.shape[0] != b or t.shape[1] != c or t.numel() != pred.numel()):
-            raise RuntimeError(f"siren_mri_amd.kspace_loss: {name} planes {tuple(t.shape)} do not match the "
-                               f"prediction {tuple(pred.shape)}")
-    for name, t in (("pred", pred), ("k0", k0), ("mask", mask), ("tgt", tgt)):
-        if t is not None and (t.dtype != torch.float32 or t.device != pred.device):
-            raise RuntimeError(f"siren_mri_amd.kspace_loss: {name} must be float32 on {pred.device}")
-    return (b, n, c, pred.contiguous(), k0.contiguous() if k0 is not None else None,
-            mask.contiguous() if mask is not None else None, tgt.contiguous())
-
-
-def _kspace_loss_cuda(pred, k0, mask, tgt, kind, noise):
-    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
-    loss = torch.empty((), dtype=torch.float32, device=pred.device)
-    ws = _sse_workspace(pred.device)
-    rc = _native.lib().siren_kspace_loss_forward(
-        int(kind), _kloss_desc_ref(kind), pc.data_ptr(), kc.data_ptr() if kc is not None else None,
-        mc.data_ptr() if mc is not None else None, tc.data_ptr(), b, n, c, float(noise), loss.data_ptr(),
-        ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
-    _native.check(rc, "siren_kspace_loss_forward")
-    return loss
-
-
-def _kspace_loss_bwd_cuda(pred, k0, mask, tgt, g, kind, noise):
-    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
-    if g.numel() != 1 or g.device != pred.device:
-        raise RuntimeError("siren_mri_amd.kspace_loss_bwd: g must be one element on the prediction's device")
-    gc = g.contiguous().to(torch.float32)
-    out = torch.empty_like(pc)
-    rc = _native.lib().siren_kspace_loss_backward(
-        int(kind), _kloss_desc_ref(kind), pc.data_ptr(), kc.data_ptr() if kc is not None else None,
-        mc.data_ptr() if mc is not None else None, tc.data_ptr(), b, n, c, float(noise), gc.data_ptr(),
-        out.data_ptr(), _native.stream_handle(pred.device))
-    _native.check(rc, "siren_kspace_loss_backward")
-    return out
-
-
-class _KspaceLossAutograd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, k0, mask, tgt, kind, noise):
-        with torch._C._AutoDispatchBelowAutograd():
-            loss = torch.ops.siren_mri_amd.kspace_loss(pred, k0, mask, tgt, kind, noise)
-        ctx.save_for_backward(pred, k0, mask, tgt)  # the op's own inputs: no residual is kept
-        ctx.kind, ctx.noise = kind, noise
-        ctx.set_materialize_grads(False)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return (None,) * 6
-        if torch.is_grad_enabled():
-            raise RuntimeError("siren_mri_amd: double backward through the native k-space loss is not provided; "
-                               "run it on the expression path (siren_mri_amd.loss_functions."
-                               "set_kspace_loss_native(False))")
-        pred, k0, mask, tgt = ctx.saved_tensors
-        dpred = torch.ops.siren_mri_amd.kspace_loss_bwd(pred, k0, mask, tgt, g, ctx.kind, ctx.noise)
-        return dpred, None, None, None, None, None
-
-
-_LIB.impl("kspace_loss", _kspace_loss_cuda, "CUDA")
-_LIB.impl("kspace_loss_bwd", _kspace_loss_bwd_cuda, "CUDA")
-_LIB.impl("kspace_loss", lambda pred, k0, mask, tgt, kind, noise:
-          _KspaceLossAutograd.apply(pred, k0, mask, tgt, kind, noise), "Autograd")
-torch.library.register_fake("siren_mri_amd::kspace_loss", lambda pred, k0, mask, tgt, kind, noise: pred.new_empty(()),
-                            lib=_LIB)
-torch.library.register_fake("siren_mri_amd::kspace_loss_bwd",
-                            lambda pred, k0, mask, tgt, g, kind, noise: torch.empty_like(pred), lib=_LIB)
-
 _KLOSS_NATIVE = True
 
 
@@ -453,165 +200,21 @@ def set_kspace_loss_native(enabled: bool) -> None:
 
 def _kspace_loss_native(out, tgt, kind):
     """A loss of the family on [B, N, C] through the native op, or None when it does not apply."""
-    if not (_KLOSS_NATIVE and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3
-            and tgt.shape == out.shape and tgt.dtype == torch.float32 and tgt.device == out.device
-            and not tgt.requires_grad and 1 <= out.shape[-1] <= 8):
+    if not (_KLOSS_NATIVE and _native_operands(out, tgt) and 1 <= out.shape[-1] <= 8):
         return None
     if kind in (_native.KLOSS_PERP, _native.KLOSS_LOG) and out.shape[-1] != 2:
         return None
-    src = dc_source(out) if _FUSE_DC else None
-    if src is not None and src[0].shape == out.shape:
-        pred, k0, mask, noise = src
-        return torch.ops.siren_mri_amd.kspace_loss(pred, k0, mask, tgt, kind, noise)
-    return torch.ops.siren_mri_amd.kspace_loss(out, None, None, tgt, kind, 0.0)
+    pred, k0, mask, noise = _fold_dc(out)
+    return torch.ops.siren_mri_amd.kspace_loss(pred, k0, mask, tgt, kind, noise)
 
-
-# The image-domain member of the family and the transform it runs on (siren_kfft.hip), on [B, side^2, 2]
-# (real, imaginary; pixels row-major as lin2img lays them out), side 8, 16, 32, 64 or 128:
-#   siren_mri_amd::kspace_fft2(x, inverse) -> torch.fft.fft2 / ifft2 of the complex slices, as [B, side^2, 2]
-#   siren_mri_amd::kspace_ift_loss(pred, k0?, mask?, tgt, img_mask?, noise, img_weight, l1_weight, kspace_weight)
-#       -> img_weight sum m (|ifft2 y| - |ifft2 t|)^2 + l1_weight sum |y| + kspace_weight sum (y - t)^2
-#   siren_mri_amd::kspace_ift_loss_bwd(the same operands, g, ...) -> dpred
-# One launch each; the backward recomputes everything from its inputs, so the forward saves no residual.
-_LIB.define("kspace_fft2(Tensor x, bool inverse) -> Tensor")
-_LIB.define("kspace_ift_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, float noise, "
-            "float img_weight, float l1_weight, float kspace_weight) -> Tensor")
-_LIB.define("kspace_ift_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, Tensor g, "
-            "float noise, float img_weight, float l1_weight, float kspace_weight) -> Tensor")
 
 # ift_image_mse's constants (loss_functions.py:207-229): image SSE, 1e-8 sum |y|, 0.0025 k-space SSE
 _IFT_WEIGHTS = (1.0, 1e-8, 0.0025)
 
 
-def _kfft_side(n):
-    """The side of an n-pixel slice the transform kernels take, or None."""
-    side = int(round(n ** 0.5))
-    return side if side * side == n and side in _native.KFFT_SIDES else None
-
-
-def _kift_max_batch():
-    """Slices per launch of the loss ops: one slot of the SSE workspace each."""
-    return (int(_native.lib().siren_sse_workspace_bytes()) - 256) // 4
-
-
-def _kfft2_cuda(x, inverse):
-    if x.dim() != 3 or x.shape[-1] != 2 or _kfft_side(x.shape[1]) is None or x.dtype != torch.float32:
-        raise RuntimeError(f"siren_mri_amd.kspace_fft2: x {tuple(x.shape)} {x.dtype} must be float32 [B, side^2, 2] "
-                           f"with side in {_native.KFFT_SIDES}")
-    xc = x.contiguous()
-    out = torch.empty_like(xc)
-    rc = _native.lib().siren_kspace_fft2(xc.data_ptr(), out.data_ptr(), xc.shape[0], _kfft_side(xc.shape[1]),
-                                         1 if inverse else 0, _native.stream_handle(x.device))
-    _native.check(rc, "siren_kspace_fft2")
-    return out
-
-
-def _kfft2_autograd(x, inverse):
-    if torch.is_grad_enabled() and x.requires_grad:
-        raise RuntimeError("siren_mri_amd.kspace_fft2 is not differentiable: detach its input (the image-domain "
-                           "loss with a gradient is siren_mri_amd.kspace_ift_loss), or use torch.fft")
-    with torch._C._AutoDispatchBelowAutograd():
-        return torch.ops.siren_mri_amd.kspace_fft2(x, inverse)
-
-
-def _kift_operands(pred, k0, mask, tgt, img_mask):
-    """Contiguous fp32 operands of the two loss ops; img_mask as (tensor or None, its batch stride)."""
-    b, n, c, pc, kc, mc, tc = _kloss_operands(pred, k0, mask, tgt)
-    side = _kfft_side(n)
-    if c != 2 or side is None:
-        raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: pred {tuple(pred.shape)} must be [B, side^2, 2] with side "
-                           f"in {_native.KFFT_SIDES}")
-    stride = 0
-    if img_mask is not None:
-        if img_mask.dtype != torch.float32 or img_mask.device != pred.device:
-            raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: img_mask must be float32 on {pred.device}")
-        if tuple(img_mask.shape) == (b, side, side) and b > 1:
-            stride = n
-        elif tuple(img_mask.shape) not in ((side, side), (1, side, side)):
-            raise RuntimeError(f"siren_mri_amd.kspace_ift_loss: img_mask {tuple(img_mask.shape)} is neither "
-                               f"[{side}, {side}] nor [{b}, {side}, {side}]")
-        img_mask = img_mask.contiguous()
-    return b, side, pc, kc, mc, tc, img_mask, stride
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _kspace_ift_loss_cuda(pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight):
-    import ctypes
-    b, side, pc, kc, mc, tc, ic, stride = _kift_operands(pred, k0, mask, tgt, img_mask)
-    loss = torch.empty((), dtype=torch.float32, device=pred.device)
-    ws = _sse_workspace(pred.device)
-    desc = _native.SirenKiftDesc(img_weight, l1_weight, kspace_weight)
-    rc = _native.lib().siren_kspace_ift_loss_forward(
-        ctypes.byref(desc), pc.data_ptr(), _ptr(kc), _ptr(mc), tc.data_ptr(), _ptr(ic), stride, b, side, float(noise),
-        loss.data_ptr(), ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
-    _native.check(rc, "siren_kspace_ift_loss_forward")
-    return loss
-
-
-def _kspace_ift_loss_bwd_cuda(pred, k0, mask, tgt, img_mask, g, noise, img_weight, l1_weight, kspace_weight):
-    import ctypes
-    b, side, pc, kc, mc, tc, ic, stride = _kift_operands(pred, k0, mask, tgt, img_mask)
-    if g.numel() != 1 or g.device != pred.device:
-        raise RuntimeError("siren_mri_amd.kspace_ift_loss_bwd: g must be one element on the prediction's device")
-    gc = g.contiguous().to(torch.float32)
-    out = torch.empty_like(pc)
-    desc = _native.SirenKiftDesc(img_weight, l1_weight, kspace_weight)
-    rc = _native.lib().siren_kspace_ift_loss_backward(
-        ctypes.byref(desc), pc.data_ptr(), _ptr(kc), _ptr(mc), tc.data_ptr(), _ptr(ic), stride, b, side, float(noise),
-        gc.data_ptr(), out.data_ptr(), _native.stream_handle(pred.device))
-    _native.check(rc, "siren_kspace_ift_loss_backward")
-    return out
-
-
-class _KspaceIftLossAutograd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight):
-        with torch._C._AutoDispatchBelowAutograd():
-            loss = torch.ops.siren_mri_amd.kspace_ift_loss(pred, k0, mask, tgt, img_mask, noise, img_weight,
-                                                           l1_weight, kspace_weight)
-        ctx.save_for_backward(pred, k0, mask, tgt, img_mask)  # the op's own inputs: no residual is kept
-        ctx.consts = (noise, img_weight, l1_weight, kspace_weight)
-        ctx.set_materialize_grads(False)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return (None,) * 9
-        if torch.is_grad_enabled():
-            raise RuntimeError("siren_mri_amd: double backward through the native image-domain k-space loss is not "
-                               "provided; run it on the expression path (siren_mri_amd.loss_functions."
-                               "set_kspace_loss_native(False))")
-        pred, k0, mask, tgt, img_mask = ctx.saved_tensors
-        dpred = torch.ops.siren_mri_amd.kspace_ift_loss_bwd(pred, k0, mask, tgt, img_mask, g, *ctx.consts)
-        return (dpred,) + (None,) * 8
-
-
-_LIB.impl("kspace_fft2", _kfft2_cuda, "CUDA")
-_LIB.impl("kspace_fft2", _kfft2_autograd, "Autograd")
-_LIB.impl("kspace_ift_loss", _kspace_ift_loss_cuda, "CUDA")
-_LIB.impl("kspace_ift_loss_bwd", _kspace_ift_loss_bwd_cuda, "CUDA")
-_LIB.impl("kspace_ift_loss", lambda pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight:
-          _KspaceIftLossAutograd.apply(pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight),
-          "Autograd")
-torch.library.register_fake("siren_mri_amd::kspace_fft2", lambda x, inverse: torch.empty_like(x), lib=_LIB)
-torch.library.register_fake(
-    "siren_mri_amd::kspace_ift_loss",
-    lambda pred, k0, mask, tgt, img_mask, noise, img_weight, l1_weight, kspace_weight: pred.new_empty(()), lib=_LIB)
-torch.library.register_fake(
-    "siren_mri_amd::kspace_ift_loss_bwd",
-    lambda pred, k0, mask, tgt, img_mask, g, noise, img_weight, l1_weight, kspace_weight: torch.empty_like(pred),
-    lib=_LIB)
-
-
 def _ift_native_applies(mask, out, tgt):
     """Whether ift_image_mse of these operands runs on siren_mri_amd::kspace_ift_loss."""
-    if not (_KLOSS_NATIVE and torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3
-            and out.shape[-1] == 2 and tgt.shape == out.shape and tgt.dtype == torch.float32
-            and tgt.device == out.device and not tgt.requires_grad):
+    if not (_KLOSS_NATIVE and torch.is_tensor(out) and _native_operands(out, tgt) and out.shape[-1] == 2):
         return False
     b, side = out.shape[0], _kfft_side(out.shape[1])
     if side is None or not 1 <= b <= _kift_max_batch():
@@ -625,11 +228,8 @@ def _ift_loss_native(mask, out, tgt):
     """ift_image_mse on [B, side^2, 2] through the native op, or None when it does not apply."""
     if not _ift_native_applies(mask, out, tgt):
         return None
-    src = dc_source(out) if _FUSE_DC else None
-    if src is not None and src[0].shape == out.shape:
-        pred, k0, planes, noise = src
-        return torch.ops.siren_mri_amd.kspace_ift_loss(pred, k0, planes, tgt, mask, noise, *_IFT_WEIGHTS)
-    return torch.ops.siren_mri_amd.kspace_ift_loss(out, None, None, tgt, mask, 0.0, *_IFT_WEIGHTS)
+    pred, k0, planes, noise = _fold_dc(out)
+    return torch.ops.siren_mri_amd.kspace_ift_loss(pred, k0, planes, tgt, mask, noise, *_IFT_WEIGHTS)
 
 
 def _complex_planes(t):

@@ -26,6 +26,29 @@ def test_ops_registered_with_schemas():
     assert "Tensor[]" in str(torch.ops.siren_mri_amd.sine_mlp_bwd.default._schema).split("->")[1]
 
 
+# the loss ops' schemas, as loss_functions.py defined them before the bindings moved to loss_ops.py
+LOSS_OP_SCHEMAS = {
+    "kspace_sse": "kspace_sse(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? hf, float noise, float weight) "
+                  "-> (Tensor, Tensor)",
+    "kspace_sse_bwd": "kspace_sse_bwd(Tensor d, Tensor? mask, Tensor? hf, Tensor g, float noise, float scale) -> Tensor",
+    "kspace_loss": "kspace_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, int kind, float noise) -> Tensor",
+    "kspace_loss_bwd": "kspace_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor g, int kind, "
+                       "float noise) -> Tensor",
+    "kspace_fft2": "kspace_fft2(Tensor x, bool inverse) -> Tensor",
+    "kspace_ift_loss": "kspace_ift_loss(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, "
+                       "float noise, float img_weight, float l1_weight, float kspace_weight) -> Tensor",
+    "kspace_ift_loss_bwd": "kspace_ift_loss_bwd(Tensor pred, Tensor? k0, Tensor? mask, Tensor tgt, Tensor? img_mask, "
+                           "Tensor g, float noise, float img_weight, float l1_weight, float kspace_weight) -> Tensor",
+}
+
+
+@pytest.mark.parametrize("name", sorted(LOSS_OP_SCHEMAS))
+def test_loss_op_schemas_are_pinned(name):
+    """Importing siren_mri_amd.loss_functions registers the seven loss ops with these schemas."""
+    op = getattr(torch.ops.siren_mri_amd, name)
+    assert str(op.default._schema) == "siren_mri_amd::" + LOSS_OP_SCHEMAS[name]
+
+
 def _fake_args(B, N, dims, batched):
     lead = (B, N) if batched else (1, N)
     x = torch.empty(*lead, dims[0], device="cuda")
