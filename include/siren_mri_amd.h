@@ -186,11 +186,17 @@ int64_t siren_mlp_backward_plan(const siren_mlp_desc* d, int flags, char* out, i
  * grad [rows, in_features]; SIREN_JVP_LAPLACE writes lap [rows] (grad is scratch of the gradient's
  * size); SIREN_JVP_JACOBIAN writes the per-channel Jacobian grad [rows, out_features, in_features]
  * (diff_operators.jacobian, diff_operators.py:46-59; and gradient() with grad_outputs that vary
- * across output channels, or any autograd double backward through the SIREN forward).
+ * across output channels, or any autograd double backward through the SIREN forward);
+ * SIREN_JVP_HESSIAN writes the per-channel Hessian grad [rows, out_features, in_features,
+ * in_features] (diff_operators.hessian, diff_operators.py:5-24; exactly symmetric; lap is unused).
+ * It needs in_features <= 3 and out_features <= 8, and carries one second-order stream per pair
+ * j <= k next to the tangents: 1 + C + C (C + 1) / 2 streams, so `saved` keeps
+ * (C + C (C + 1) / 2) * 4 bytes per row and hidden feature.
  */
 #define SIREN_JVP_GRADIENT 1
 #define SIREN_JVP_LAPLACE 2
 #define SIREN_JVP_JACOBIAN 3
+#define SIREN_JVP_HESSIAN 4
 int64_t siren_jvp_saved_bytes(const siren_mlp_desc* d, int order);
 int64_t siren_jvp_workspace_bytes(const siren_mlp_desc* d, int order);
 int siren_jvp_forward(const siren_mlp_desc* d, int order, const float* x, float* grad, float* lap,
@@ -200,11 +206,12 @@ int siren_jvp_forward(const siren_mlp_desc* d, int order, const float* x, float*
 /*
  * Backward of a loss on the gradient (order 1), the Laplacian (order 2) or the Jacobian (order 3):
  * from dgrad = dL/dgrad [rows, in_features] (order 1), dL/dlap [rows] (order 2) or
- * dL/djac [rows, out_features, in_features] (order 3) writes
+ * dL/djac [rows, out_features, in_features] (order 3) or dL/dhess [rows, out_features,
+ * in_features, in_features] (order 4; any tensor, it need not be symmetric) writes
  * dweight/dbias (overwrite; the output bias gets zeros: it does not reach either derivative)
  * and, if dx != NULL, dx. These are the double / triple backward passes that
- * loss_functions.gradients_mse (loss_functions.py:330-335) and laplace_mse (:350-355) run
- * through autograd. `saved` must come from siren_jvp_forward with the same order.
+ * loss_functions.gradients_mse (loss_functions.py:330-335), laplace_mse (:350-355) and
+ * image_mse_FH_prior (:255-272) run through autograd. `saved` must come from siren_jvp_forward with the same order.
  */
 int siren_jvp_backward(const siren_mlp_desc* d, int order, const float* x, const float* dgrad,
                        const void* saved, int64_t saved_bytes, void* workspace,

@@ -26,9 +26,10 @@ JLayout jlayout_of(const siren_mlp_desc* d, int order) {
   memset(&jl, 0, sizeof(jl));
   jl.base = layout_of(d);
   jl.C = d->dims[0];
-  jl.Su = jl.C + (order == SIREN_JVP_LAPLACE ? 1 : 0);
+  // stored U planes: the C tangents, then the Laplacian's V or the Hessian's C (C + 1) / 2 pair streams
+  jl.Su = jl.C + (order == SIREN_JVP_LAPLACE ? 1 : order == SIREN_JVP_HESSIAN ? jl.C * (jl.C + 1) / 2 : 0);
   jl.S = 1 + jl.Su;
-  jl.Sb = 1 + jl.Su;  // adjoints [a_bar; u_bar^k (; V_bar)] mirror the forward streams
+  jl.Sb = 1 + jl.Su;  // adjoints [a_bar; u_bar^k (; V_bar / V_bar^{jk})] mirror the forward streams
   int64_t off = jl.base.weights_bytes;
   for (int l = 0; l + 1 < g.L; ++l) {
     jl.p_off[l] = off;
@@ -69,10 +70,15 @@ JLayout jlayout_of(const siren_mlp_desc* d, int order) {
 int jvp_check(const siren_mlp_desc* d, int order) {
   int rc = siren_mlp_check(d);
   if (rc) return rc;
-  if (order != SIREN_JVP_GRADIENT && order != SIREN_JVP_LAPLACE && order != SIREN_JVP_JACOBIAN)
-    return fail(SIREN_EINVAL, "derivative mode %d unsupported (1 gradient, 2 Laplacian, 3 Jacobian)", order);
+  if (order != SIREN_JVP_GRADIENT && order != SIREN_JVP_LAPLACE && order != SIREN_JVP_JACOBIAN &&
+      order != SIREN_JVP_HESSIAN)
+    return fail(SIREN_EINVAL, "derivative mode %d unsupported (1 gradient, 2 Laplacian, 3 Jacobian, 4 Hessian)", order);
   if (!d->outermost_linear) return fail(SIREN_EINVAL, "analytic derivatives need outermost_linear");
   if (d->dims[0] > 4) return fail(SIREN_EINVAL, "analytic derivatives support in_features <= 4");
+  if (order == SIREN_JVP_HESSIAN && d->dims[0] > 3)
+    return fail(SIREN_EINVAL, "the analytic Hessian supports in_features <= 3 (got %d)", d->dims[0]);
+  if (order == SIREN_JVP_HESSIAN && d->dims[d->num_layers] > FUSED_MAXO)
+    return fail(SIREN_EINVAL, "the analytic Hessian supports out_features <= %d", FUSED_MAXO);
   return SIREN_OK;
 }
 
@@ -90,6 +96,7 @@ int jvp_forward_impl(const siren_mlp_desc* d, int order, const float* x, float* 
   // primal given: layer l's phases are the plain forward's saved P_l (siren_mlp_forward's layout),
   // and only the tangent streams run (stacked rows N .. S N)
   auto pptr = [&](int l) -> char* { return primal ? (char*)primal + jl.base.saved_off[l] : store + jl.p_off[l]; };
+  const bool hess = order == SIREN_JVP_HESSIAN;
   {
     JFirstArgs a;
     a.x = x;
@@ -127,7 +134,8 @@ int jvp_forward_impl(const siren_mlp_desc* d, int order, const float* x, float* 
     a.K = d->dims[l];
     a.Nout = d->dims[l + 1];
     a.w0 = d->w0;
-    if (PREC == kPrecF32 && primal && !a.lap && g_jvp_tan && jl.C >= 1 && jl.C <= 4 && a.Nout <= JADJ_BN &&
+    // (the row-stacked tile carries the tangents alone: not for the modes with second-order streams)
+    if (PREC == kPrecF32 && primal && !a.lap && !hess && g_jvp_tan && jl.C >= 1 && jl.C <= 4 && a.Nout <= JADJ_BN &&
         a.K % JNT_KC == 0) {
       // the tangent streams only, stacked by row: one phase load and cosine per element
       JTanArgs t;
@@ -155,6 +163,7 @@ int jvp_forward_impl(const siren_mlp_desc* d, int order, const float* x, float* 
     }
     dim3 grid((unsigned)cdiv((int64_t)jl.S * g.rows - a.srow0, JNT_BM), (unsigned)cdiv(a.Nout, JNT_BN), (unsigned)g.nb);
     if (a.lap) hipLaunchKernelGGL((jvp_nt_kernel<PREC, JMODE_FWD, true>), grid, dim3(256), 0, st, a);
+    else if (hess) hipLaunchKernelGGL((jvp_nt_kernel<PREC, JMODE_FWD, false, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((jvp_nt_kernel<PREC, JMODE_FWD>), grid, dim3(256), 0, st, a);
     if ((rc = check_launch("jvp_nt fwd"))) return rc;
   }
@@ -174,11 +183,29 @@ int jvp_forward_impl(const siren_mlp_desc* d, int order, const float* x, float* 
     a.Su = jl.Su;
     a.w_bstride = d->weights_batched ? (int64_t)d->dims[l + 1] * d->dims[l] : 0;
     a.w0 = d->w0;
-    hipLaunchKernelGGL(jvp_last_kernel<PREC>, dim3((unsigned)std::min<int64_t>(cdiv(g.rows, 8), 4096 / g.nb + 1), (unsigned)g.nb),
-                       dim3(256), 0, st, a);
+    const dim3 lgrid((unsigned)std::min<int64_t>(cdiv(g.rows, 8), 4096 / g.nb + 1), (unsigned)g.nb);
+    if (hess) {  // grad is the per-channel Hessian [rows][O][C][C]
+      switch (jl.C) {
+        case 1: hipLaunchKernelGGL((jvp_last_hess_kernel<PREC, 1>), lgrid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((jvp_last_hess_kernel<PREC, 2>), lgrid, dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((jvp_last_hess_kernel<PREC, 3>), lgrid, dim3(256), 0, st, a); break;
+      }
+    } else {
+      hipLaunchKernelGGL(jvp_last_kernel<PREC>, lgrid, dim3(256), 0, st, a);
+    }
     if ((rc = check_launch("jvp_last"))) return rc;
   }
   return SIREN_OK;
+}
+
+// jvp_hess_combine_kernel for C = 1..3 tangents (jvp_check)
+template <int PREC, bool TOP>
+void launch_hess_combine(int C, dim3 grid, hipStream_t st, const JCombArgs& a) {
+  switch (C) {
+    case 1: hipLaunchKernelGGL((jvp_hess_combine_kernel<PREC, 1, TOP>), grid, dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((jvp_hess_combine_kernel<PREC, 2, TOP>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((jvp_hess_combine_kernel<PREC, 3, TOP>), grid, dim3(256), 0, st, a); break;
+  }
 }
 
 // jvp_tn2_kernel (fp32 weight gradient of a hidden layer): dW of 256 rows (the layer's width M), input
@@ -206,6 +233,7 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
   const JLayout jl = jlayout_of(d, order);
   auto pptr = [&](int l) -> const char* { return primal ? primal + jl.base.saved_off[l] : saved + jl.p_off[l]; };
   const int lapmode = order == SIREN_JVP_LAPLACE;
+  const bool hess = order == SIREN_JVP_HESSIAN;
   float* part = (float*)(ws + jl.part_off);
   int rc = SIREN_OK;
   int cur = 0;
@@ -234,7 +262,9 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
     a.w_bstride = d->weights_batched ? (int64_t)d->dims[l + 1] * d->dims[l] : 0;
     a.w0 = d->w0;
     a.jac = order == SIREN_JVP_JACOBIAN;
-    if (a.jac)
+    if (hess)
+      launch_hess_combine<PREC, true>(jl.C, dim3((unsigned)s.nsplit, (unsigned)g.nb), st, a);
+    else if (a.jac)
       hipLaunchKernelGGL(jvp_combine_jac_kernel<PREC>, dim3((unsigned)s.nsplit, (unsigned)g.nb), dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL(jvp_combine_kernel<PREC>, dim3((unsigned)s.nsplit, (unsigned)g.nb), dim3(256), 0, st, a);
@@ -261,7 +291,7 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
       a.M = M;
       a.Kin = N;
       a.w0 = d->w0;
-      if (PREC == kPrecF32 && jvp_tn2_ok(M, N)) {
+      if (PREC == kPrecF32 && !hess && jvp_tn2_ok(M, N)) {  // (jvp_tn2_kernel has no pair-stream operand)
         // fp32: all 256 dW rows per workgroup (jvp_tn2_kernel), with its own, smaller split count
         const Split s2 = jtn2_split(g, (int64_t)jl.Sb * g.rows, N);
         a.rows_per_split = s2.rows_per_split;
@@ -275,6 +305,7 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
       } else {
         dim3 grid((unsigned)(cdiv(M, 128) * cdiv(N, 128)), (unsigned)s.nsplit, (unsigned)g.nb);
         if (lapmode) hipLaunchKernelGGL((jvp_tn_kernel<PREC, true>), grid, dim3(256), 0, st, a);
+        else if (hess) hipLaunchKernelGGL((jvp_tn_kernel<PREC, false, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((jvp_tn_kernel<PREC>), grid, dim3(256), 0, st, a);
         if ((rc = check_launch("jvp_tn"))) return rc;
         if ((rc = launch_reduce(part, s.nsplit, a.split_stride, g.nb, (int64_t)M * N + M, (int64_t)M * N,
@@ -282,7 +313,7 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
           return rc;
       }
     }
-    if (jvp_adj_fused(jl.Sb, lapmode, N)) {
+    if (!hess && jvp_adj_fused(jl.Sb, lapmode, N)) {  // (jvp_adj_kernel's combine has no pair streams)
       // adjoint GEMM + combine in one launch (jvp_adj_kernel)
       JAdjArgs a;
       a.D = ws + jl.d_off[cur];
@@ -342,7 +373,8 @@ int jvp_backward_impl(const siren_mlp_desc* d, int order, const float* x, const 
       a.top = 0;
       a.lap = lapmode;
       a.w0 = d->w0;
-      hipLaunchKernelGGL(jvp_combine_kernel<PREC>, dim3((unsigned)s.nsplit, (unsigned)g.nb), dim3(256), 0, st, a);
+      if (hess) launch_hess_combine<PREC, false>(jl.C, dim3((unsigned)s.nsplit, (unsigned)g.nb), st, a);
+      else hipLaunchKernelGGL(jvp_combine_kernel<PREC>, dim3((unsigned)s.nsplit, (unsigned)g.nb), dim3(256), 0, st, a);
       if ((rc = check_launch("jvp_combine"))) return rc;
       cur ^= 1;
     }

@@ -23,6 +23,20 @@
 //   [h_bar; t_bar^k; S_bar]_{l-1} = D W_l
 //   first layer: W_bar_0 = a_bar^T x + [sum_n u_bar^k as column k] ; x_bar = a_bar W_0 (V_0 = 0)
 // (order 1 has no S stream: S_bar = 0; the Laplacian loss has no gradient stream at the top)
+//
+// The per-channel Hessian (diff_operators.hessian, SIREN_JVP_HESSIAN) keeps the second-order streams
+// apart: after the primal and the C tangents come NP = C (C + 1) / 2 streams S^{jk}, one per pair
+// 0 <= j <= k < C in row-major order over the upper triangle (pair p of stream 1 + C + p):
+//   V_l^{jk} = W_l S_{l-1}^{jk}      S_l^{jk} = w0 c V_l^{jk} - w0^2 s u_l^j u_l^k      (V_0^{jk} = 0)
+//   hess[n][o][j][k] = hess[n][o][k][j] = sum_f W_L[o][f] S_{L-1}^{jk}[f]
+// and its adjoint, for any cotangent G with Gh^{jk} = G[n][o][j][k] + (j != k) G[n][o][k][j]:
+//   top:   S_bar^{jk}[f] = sum_o Gh^{jk} W_L[o][f], t_bar = h_bar = 0,
+//          W_bar_L[o][f] = sum_n sum_{j<=k} Gh^{jk} S_{L-1}^{jk}[f]
+//   layer: V_bar^{jk} = w0 c S_bar^{jk}
+//          u_bar^m = w0 c t_bar^m - w0^2 s sum_{j<=k} S_bar^{jk} (d_jm u^k + d_km u^j)
+//          a_bar   = w0 (c h_bar - w0 s sum_k t_bar^k u^k - w0 sum_{j<=k} S_bar^{jk} (s V^{jk} + w0 c u^j u^k))
+// (S_bar^{jk} = d_jk S_bar gives the Laplacian's formulas above); the GEMMs, W_bar_l, b_bar_l and the
+// first layer run over the 1 + C + NP stacked streams as for the other modes.
 #include "siren_common.h"
 
 namespace siren {
@@ -86,8 +100,22 @@ DEV void jvp_operand4(const JNTArgs& a, int64_t b, int s, int64_t n, int k, floa
   }
 }
 
+// Pair p of the Hessian's second-order streams -> (j, k), 0 <= j <= k < C, row-major over the
+// upper triangle.
+DEV void hess_pair(int C, int p, int& j, int& k) {
+  j = 0;
+  int len = C;
+  while (p >= len) {
+    p -= len;
+    --len;
+    ++j;
+  }
+  k = j + p;
+}
+
 // LAP: the operand has a Laplacian stream (order 2); the gradient / Jacobian forms omit its code.
-template <int PREC, int MODE, bool LAP = false>
+// HESS: the streams after the C tangents are the Hessian's pair streams S^{jk} (order 4).
+template <int PREC, int MODE, bool LAP = false, bool HESS = false>
 __global__ __launch_bounds__(256) void jvp_nt_kernel(JNTArgs a) {
   using PT = Prec<PREC>;
   using phase_t = typename PT::phase_t;
@@ -132,6 +160,17 @@ __global__ __launch_bounds__(256) void jvp_nt_kernel(JNTArgs a) {
     sq[q] = row < rows ? (int)(row / a.N) : -1;
     nq[q] = row < rows ? row - (int64_t)sq[q] * a.N : 0;
   }
+  // HESS: the tangent planes (j, k) of a pair-stream unit, and their raw values: fetched in load()
+  // with the unit's V^{jk} plane (uraw), like every other raw operand
+  int hj[HESS ? 4 : 1], hk[HESS ? 4 : 1];
+  float ujraw[HESS ? 4 : 1][4], ukraw[HESS ? 4 : 1][4];
+  if constexpr (HESS && MODE == JMODE_FWD) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      hj[q] = hk[q] = 0;
+      if (sq[q] > a.C) hess_pair(a.C, sq[q] - 1 - a.C, hj[q], hk[q]);
+    }
+  }
   const int64_t plane = a.N * (int64_t)K;
   auto load = [&](int k0) {
 #pragma unroll
@@ -153,13 +192,25 @@ __global__ __launch_bounds__(256) void jvp_nt_kernel(JNTArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) praw[q][e] = pv[e];
           }
-          if (s >= 1 && s <= a.C) {
+          if (s >= 1 && (HESS || s <= a.C)) {  // (HESS: a pair stream's plane s - 1 holds V^{jk})
             const f32x4 uv = *(const f32x4*)(a.U + b * (int64_t)(a.S - 1) * plane + (int64_t)(s - 1) * plane + n * K + k);
 #pragma unroll
             for (int e = 0; e < 4; ++e) uraw[q][e] = uv[e];
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) uraw[q][e] = 0.f;
+          }
+          if constexpr (HESS) {
+            if (s > a.C) {
+              const float* Ub = a.U + b * (int64_t)(a.S - 1) * plane + n * K + k;
+              const f32x4 uj = *(const f32x4*)(Ub + (int64_t)hj[q] * plane);
+              const f32x4 uk = *(const f32x4*)(Ub + (int64_t)hk[q] * plane);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                ujraw[q][e] = uj[e];
+                ukraw[q][e] = uk[e];
+              }
+            }
           }
         } else {
           const grad_t* D = (const grad_t*)a.D + (b * rows + m0 + (u >> 3)) * K + k;
@@ -208,12 +259,18 @@ __global__ __launch_bounds__(256) void jvp_nt_kernel(JNTArgs a) {
         if (s == 0) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) areg[q][e] = PT::sinp(praw[q][e]);
-        } else if (!LAP || s <= a.C) {
+        } else if (!(LAP || HESS) || s <= a.C) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) areg[q][e] = a.w0 * PT::cosp(praw[q][e]) * uraw[q][e];
         } else {
           if constexpr (LAP)  // the Laplacian stream (C + 1 tangent planes): from memory
             jvp_operand4<PREC>(a, b, s, nq[q], k0 + ((tid + 256 * q) & 7) * 4, areg[q]);
+          if constexpr (HESS) {  // a pair stream: S^{jk} = w0 c V^{jk} - w0^2 s u^j u^k
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              areg[q][e] = a.w0 * PT::cosp(praw[q][e]) * uraw[q][e] -
+                           a.w0 * a.w0 * PT::sinp(praw[q][e]) * ujraw[q][e] * ukraw[q][e];
+          }
         }
       }
     }
@@ -340,7 +397,7 @@ struct JTNArgs {
   float w0;
 };
 
-template <int PREC, bool LAP = false>
+template <int PREC, bool LAP = false, bool HESS = false>
 __global__ __launch_bounds__(256) void jvp_tn_kernel(JTNArgs a) {
   using PT = Prec<PREC>;
   using phase_t = typename PT::phase_t;
@@ -378,6 +435,7 @@ __global__ __launch_bounds__(256) void jvp_tn_kernel(JTNArgs a) {
   // from one division per chunk (rows of a chunk are consecutive).
   const int cu = tid & 127, ru = tid >> 7;
   float draw[16], uraw[16];
+  float ujraw[HESS ? 16 : 1], ukraw[HESS ? 16 : 1];  // HESS: a pair-stream row's u^j, u^k (uraw: its V^{jk})
   phase_t praw[16];
   // (stream, row) of the chunk's row r from the chunk's first row (s0, n0): one scalar division
   // per chunk, outside the unrolled per-row loops
@@ -405,7 +463,17 @@ __global__ __launch_bounds__(256) void jvp_tn_kernel(JTNArgs a) {
         if (i0 + cu < a.M) draw[q] = to_f32(((const grad_t*)a.D)[(b * rows + row) * a.M + i0 + cu]);
         if (j0 + cu < a.Kin) {
           praw[q] = ((const phase_t*)a.P)[(b * a.N + n) * a.Kin + j0 + cu];
-          if (s >= 1 && s <= a.C) uraw[q] = a.U[b * a.Su * plane + (int64_t)(s - 1) * plane + n * a.Kin + j0 + cu];
+          if (s >= 1 && (HESS || s <= a.C))
+            uraw[q] = a.U[b * a.Su * plane + (int64_t)(s - 1) * plane + n * a.Kin + j0 + cu];
+          if constexpr (HESS) {
+            if (s > a.C) {
+              int hj, hk;
+              hess_pair(a.C, s - 1 - a.C, hj, hk);
+              const float* Ue = a.U + b * a.Su * plane + n * a.Kin + j0 + cu;
+              ujraw[q] = Ue[(int64_t)hj * plane];
+              ukraw[q] = Ue[(int64_t)hk * plane];
+            }
+          }
         }
       }
     }
@@ -429,8 +497,10 @@ __global__ __launch_bounds__(256) void jvp_tn_kernel(JTNArgs a) {
           const phase_t p = praw[q];
           if (s == 0) {
             xv = PT::sinp(p);
-          } else if (!LAP || s <= a.C) {
+          } else if (!(LAP || HESS) || s <= a.C) {
             xv = a.w0 * PT::cosp(p) * uraw[q];
+          } else if constexpr (HESS) {  // pair stream: S^{jk} = w0 c V^{jk} - w0^2 s u^j u^k
+            xv = a.w0 * PT::cosp(p) * uraw[q] - a.w0 * a.w0 * PT::sinp(p) * ujraw[q] * ukraw[q];
           } else if constexpr (LAP) {  // Laplacian stream: S = w0 c V - w0^2 s Q (C + 1 planes from memory)
             const float* Ue = a.U + b * a.Su * plane + n * a.Kin + j0 + cu;
             float qq = 0.f;
@@ -796,6 +866,58 @@ __global__ __launch_bounds__(256) void jvp_last_kernel(JLastArgs a) {
   }
 }
 
+// Output layer of the per-channel Hessian (SIREN_JVP_HESSIAN): a.grad is [B][N][O][C][C],
+// hess[n][o][j][k] = hess[n][o][k][j] = sum_f W[o][f] S^{jk}[f], S^{jk} = w0 c V^{jk} - w0^2 s u^j u^k
+// (both triangles stored from the same register: exactly symmetric). One half-wave per row, one
+// pass over the row per output channel (as the Jacobian form of jvp_last_kernel).
+template <int PREC, int C>
+__global__ __launch_bounds__(256) void jvp_last_hess_kernel(JLastArgs a) {
+  using PT = Prec<PREC>;
+  using phase_t = typename PT::phase_t;
+  constexpr int NP = C * (C + 1) / 2;
+  const int l32 = threadIdx.x & 31;
+  const int64_t b = blockIdx.y;
+  const float* W = a.W + b * a.w_bstride;
+  const int64_t plane = a.N * (int64_t)a.F;
+  const float w0 = a.w0, w02 = a.w0 * a.w0;
+  for (int64_t n = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5); n < a.N; n += (int64_t)gridDim.x * 8) {
+    for (int o = 0; o < a.O; ++o) {
+      float hs[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) hs[p] = 0.f;
+      for (int f = l32; f < a.F; f += 32) {
+        const phase_t ph = ((const phase_t*)a.P)[(b * a.N + n) * a.F + f];
+        const float w = W[o * a.F + f];
+        const float wc = w * w0 * PT::cosp(ph), wsn = w * w02 * PT::sinp(ph);
+        const float* Ub = a.U + b * (int64_t)a.Su * plane + n * a.F + f;
+        float u[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) u[k] = Ub[(int64_t)k * plane];
+        int p = 0;
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+          for (int k = j; k < C; ++k, ++p)
+            hs[p] = fmaf(wc, Ub[(int64_t)(C + p) * plane], fmaf(-wsn, u[j] * u[k], hs[p]));
+      }
+      float* dst = a.grad + ((b * a.N + n) * a.O + o) * (C * C);
+      int p = 0;
+#pragma unroll
+      for (int j = 0; j < C; ++j)
+#pragma unroll
+        for (int k = j; k < C; ++k, ++p) {
+          float v = hs[p];
+#pragma unroll
+          for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off, 32);
+          if (l32 == 0) {
+            dst[j * C + k] = v;
+            dst[k * C + j] = v;
+          }
+        }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Adjoint combine for a sine layer: from [h_bar; t_bar^k; S_bar] to D = [a_bar; u_bar^k; V_bar].
 // top = 1: the output layer's adjoint, t_bar^k[f] = gbar[n][k] ws[f], S_bar[f] = lbar[n] ws[f]
@@ -955,6 +1077,110 @@ __global__ __launch_bounds__(256) void jvp_combine_kernel(JCombArgs a) {
     if (a.top) {
       float* part = a.part + (int64_t)blockIdx.x * a.split_stride + b * (int64_t)(a.O * a.F + a.O);
       for (int o = 0; o < a.O; ++o) part[o * a.F + f] = dwl;
+      if (f < a.O) part[a.O * a.F + f] = 0.f;
+    }
+  }
+}
+
+// Adjoint combine of the per-channel Hessian (SIREN_JVP_HESSIAN; formulas in the header): S = 1 + C
+// + NP adjoint streams D = [a_bar; u_bar^1..C; V_bar^{jk}], the pair streams in hess_pair's order.
+// TOP: from the cotangent gbar = dL/dhess [B][N][O][C][C] (any tensor: both triangles are read),
+//      with the output layer's weight-gradient partials, as jvp_combine_jac_kernel;
+// else: from raw = [h_bar; t_bar^1..C; S_bar^{jk}] (fp32, [B][S][N][F]) of the adjoint GEMM.
+// Its own kernel (not a mode of jvp_combine_kernel): C = 3 has 10 streams, more than that kernel's
+// register arrays hold. Thread per feature column, rows of its split in order.
+template <int PREC, int C, bool TOP>
+__global__ __launch_bounds__(256) void jvp_hess_combine_kernel(JCombArgs a) {
+  using PT = Prec<PREC>;
+  using phase_t = typename PT::phase_t;
+  using grad_t = typename PT::grad_t;
+  constexpr int NP = C * (C + 1) / 2;
+  constexpr int S = 1 + C + NP;
+  const int64_t b = blockIdx.y;
+  const int64_t plane = a.N * (int64_t)a.F;
+  const float w0 = a.w0, w02 = a.w0 * a.w0;
+  grad_t* D = (grad_t*)a.D + b * S * plane;
+  const int64_t r_begin = (int64_t)blockIdx.x * a.rows_per_split;
+  const int64_t r_end = min(r_begin + a.rows_per_split, a.N);
+  for (int f = threadIdx.x; f < a.F; f += 256) {
+    float wl[TOP ? FUSED_MAXO : 1], dwl[TOP ? FUSED_MAXO : 1];
+    if constexpr (TOP) {
+      const float* WL = a.WL + b * a.w_bstride;
+#pragma unroll
+      for (int o = 0; o < FUSED_MAXO; ++o) {
+        wl[o] = o < a.O ? WL[o * a.F + f] : 0.f;
+        dwl[o] = 0.f;
+      }
+    }
+    for (int64_t n = r_begin; n < r_end; ++n) {
+      const int64_t idx = n * a.F + f;
+      const phase_t ph = ((const phase_t*)a.P)[b * plane + idx];
+      const float* Ub = a.U + b * (int64_t)a.Su * plane + idx;
+      float u[C], v[NP], tbar[C], sbar[NP];
+#pragma unroll
+      for (int k = 0; k < C; ++k) u[k] = Ub[(int64_t)k * plane];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) v[p] = Ub[(int64_t)(C + p) * plane];
+      float hbar = 0.f;
+      if constexpr (!TOP) {
+        const float* rw = a.raw + b * S * plane + idx;
+        hbar = rw[0];
+#pragma unroll
+        for (int k = 0; k < C; ++k) tbar[k] = rw[(int64_t)(1 + k) * plane];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) sbar[p] = rw[(int64_t)(1 + C + p) * plane];
+      }
+      const float c = PT::cosp(ph), s = PT::sinp(ph);
+      if constexpr (TOP) {
+        const float* gb = a.gbar + (b * a.N + n) * (int64_t)a.O * (C * C);
+#pragma unroll
+        for (int k = 0; k < C; ++k) tbar[k] = 0.f;
+        int p = 0;
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+          for (int k = j; k < C; ++k, ++p) {
+            const float sv = w0 * c * v[p] - w02 * s * u[j] * u[k];  // S^{jk}[f]
+            float sb = 0.f;
+#pragma unroll
+            for (int o = 0; o < FUSED_MAXO; ++o) {
+              if (o < a.O) {
+                float gh = gb[o * (C * C) + j * C + k];
+                if (j != k) gh += gb[o * (C * C) + k * C + j];
+                sb = fmaf(gh, wl[o], sb);
+                dwl[o] = fmaf(gh, sv, dwl[o]);
+              }
+            }
+            sbar[p] = sb;
+          }
+      }
+      float ub[C];
+      float cross = 0.f, second = 0.f;
+#pragma unroll
+      for (int k = 0; k < C; ++k) {
+        ub[k] = w0 * c * tbar[k];
+        cross = fmaf(tbar[k], u[k], cross);
+      }
+      int p = 0;
+#pragma unroll
+      for (int j = 0; j < C; ++j)
+#pragma unroll
+        for (int k = j; k < C; ++k, ++p) {
+          const float sb = sbar[p];
+          ub[j] -= w02 * s * sb * u[k];
+          ub[k] -= w02 * s * sb * u[j];
+          second = fmaf(sb, s * v[p] + w0 * c * u[j] * u[k], second);
+          D[(int64_t)(1 + C + p) * plane + idx] = from_f32<grad_t>(w0 * c * sb);
+        }
+#pragma unroll
+      for (int k = 0; k < C; ++k) D[(int64_t)(1 + k) * plane + idx] = from_f32<grad_t>(ub[k]);
+      D[idx] = from_f32<grad_t>(w0 * (c * hbar - w0 * s * cross - w0 * second));
+    }
+    if constexpr (TOP) {
+      float* part = a.part + (int64_t)blockIdx.x * a.split_stride + b * (int64_t)(a.O * a.F + a.O);
+#pragma unroll
+      for (int o = 0; o < FUSED_MAXO; ++o)
+        if (o < a.O) part[o * a.F + f] = dwl[o];
       if (f < a.O) part[a.O * a.F + f] = 0.f;
     }
   }

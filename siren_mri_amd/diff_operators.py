@@ -7,7 +7,7 @@ jacobian        diff_operators.py:46-59
 hessian         diff_operators.py:5-24
 
 For y produced by a SIREN (SingleBVPNet / FCBlock with nonlinearity='sine') w.r.t. its own
-`model_in`, gradient() and laplace() do not build an autograd graph: they call the native
+`model_in`, gradient(), laplace(), jacobian() and hessian() do not build an autograd graph: they call the native
 forward-mode (tangent-stream) kernels, which carry dh/dx (and d2h/dx2) analytically through
 every layer next to the primal activations, and whose backward is the hand-derived second-order
 adjoint. Any other (y, x) pair goes through torch.autograd exactly as the reference does.
@@ -120,7 +120,15 @@ def jacobian(y, x):
 
 
 def hessian(y, x):
-    """Hessian [B, N, C_out, C_in, C_in] and a NaN status flag."""
+    """Hessian [B, N, C_out, C_in, C_in] and a NaN status flag (for a SIREN output of at most 3
+    input dimensions: the tangent-stream op with one second-order stream per pair j <= k, one
+    native forward, differentiable; any other pair: out x in rounds of autograd, as the reference)."""
+    if _ANALYTIC and y.dim() == 3 and x.shape[-1] <= 3 and y.shape[-1] <= 8:
+        src = _lookup(y, x)
+        if src is not None:
+            from .jvp import siren_hessian
+            h = siren_hessian(x, *src, primal=_primal(y))
+            return h, (-1 if torch.any(torch.isnan(h)) else 0)
     b, n = y.shape[:2]
     grad_y = torch.ones_like(y[..., 0])
     h = torch.zeros(b, n, y.shape[-1], x.shape[-1], x.shape[-1], device=y.device)

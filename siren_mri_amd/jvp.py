@@ -11,6 +11,10 @@ siren_jacobian(x, fcblock, params) == diff_operators.jacobian(y, x)[0] (diff_ope
     dy_c/dx_k per output channel. Differentiable (the same adjoint with a per-channel cotangent);
     it also carries gradient(y, x, grad_outputs=g) for any g, and the double backward of the
     SIREN forward through autograd (ops._SineMLPAutograd under create_graph=True).
+siren_hessian(x, fcblock, params) == diff_operators.hessian(y, x)[0] (diff_operators.py:5-24):
+    d2y_c/dx_j dx_k per output channel, [..., out, in, in], exactly symmetric; in_features <= 3.
+    Differentiable: its backward carries one adjoint stream per pair j <= k (what
+    image_mse_FH_prior's triple backward computes through autograd in the reference).
 
 Custom ops (torch.library.Library "siren_mri_amd", with fake kernels and an Autograd-key
 formula), over the C ABI siren_jvp_forward/backward:
@@ -45,7 +49,7 @@ def _jvp_sizes(geo, prec, order):
     return saved, L.siren_jvp_workspace_bytes(ctypes.byref(d), order)
 
 
-GRADIENT, LAPLACE, JACOBIAN = 1, 2, 3  # SIREN_JVP_* of include/siren_mri_amd.h
+GRADIENT, LAPLACE, JACOBIAN, HESSIAN = 1, 2, 3, 4  # SIREN_JVP_* of include/siren_mri_amd.h
 
 _LIB.define("sine_mlp_jvp(Tensor x, Tensor[] weights, Tensor[] biases, float w0, int prec, bool batched, int order, "
             "bool keep, Tensor? primal=None) -> (Tensor, Tensor)")
@@ -53,10 +57,23 @@ _LIB.define("sine_mlp_jvp_bwd(Tensor dout, Tensor x, Tensor[] weights, Tensor[] 
             "int prec, bool batched, int order, bool need_dx, Tensor? primal=None) -> (Tensor, Tensor[], Tensor[])")
 
 
+def _out_shape(xshape, out_features, order):
+    """Shape of the op's result for x of shape `xshape`."""
+    lead, cin = tuple(xshape[:-1]), xshape[-1]
+    if order == GRADIENT:
+        return lead + (cin,)
+    if order == JACOBIAN:
+        return lead + (out_features, cin)
+    if order == HESSIAN:
+        return lead + (out_features, cin, cin)
+    return lead + (1,)
+
+
 def sine_mlp_jvp(x: Tensor, weights: List[Tensor], biases: List[Tensor], w0: float, prec: int, batched: bool,
                  order: int, keep: bool, primal: Tensor | None = None) -> Tuple[Tensor, Tensor]:
     """siren_jvp_forward_ex: order 1 -> sum_c dy_c/dx (shape of x); order 2 -> the Laplacian [.., 1];
-    order 3 -> the per-channel Jacobian dy_c/dx_k [.., out, in]. primal: the saved buffer of the
+    order 3 -> the per-channel Jacobian dy_c/dx_k [.., out, in]; order 4 -> the per-channel Hessian
+    [.., out, in, in]. primal: the saved buffer of the
     plain forward of this stack on this x (fp32): its phases are the primal stream."""
     _require_device(x)
     geo = _geo_of(x, weights, batched)
@@ -68,7 +85,7 @@ def sine_mlp_jvp(x: Tensor, weights: List[Tensor], biases: List[Tensor], w0: flo
     saved_bytes, ws_bytes = _jvp_sizes(geo, prec, order)
     saved = torch.empty(saved_bytes if keep else 0, dtype=torch.uint8, device=dev)
     work = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-    gshape = xc.shape[:-1] + (geo.dims[-1], xc.shape[-1]) if order == JACOBIAN else xc.shape
+    gshape = _out_shape(xc.shape, geo.dims[-1], order if order != LAPLACE else GRADIENT)
     grad = torch.empty(gshape, dtype=torch.float32, device=dev)
     lap = torch.empty(xc.shape[:-1] + (1,), dtype=torch.float32, device=dev) if order == LAPLACE else None
     rc = _native.lib().siren_jvp_forward_ex(ctypes.byref(desc), order, xc.data_ptr(), grad.data_ptr(),
@@ -84,10 +101,7 @@ def sine_mlp_jvp(x: Tensor, weights: List[Tensor], biases: List[Tensor], w0: flo
 def _sine_mlp_jvp_fake(x, weights, biases, w0, prec, batched, order, keep, primal=None):
     geo = _geo_of(x, weights, batched)
     saved_bytes, _ = _jvp_sizes(geo, prec, order)
-    if order == JACOBIAN:
-        out = x.new_empty(x.shape[:-1] + (geo.dims[-1], x.shape[-1]))
-    else:
-        out = x.new_empty(x.shape) if order == GRADIENT else x.new_empty(x.shape[:-1] + (1,))
+    out = x.new_empty(_out_shape(x.shape, geo.dims[-1], order))
     return out, x.new_empty((saved_bytes if keep else 0,), dtype=torch.uint8)
 
 
@@ -206,6 +220,12 @@ def siren_laplace(x, fcblock, params=None, primal=None):
 def siren_jacobian(x, fcblock, params=None, primal=None):
     """dy_c/dx_k per output channel, [..., out_features, in_features] (diff_operators.jacobian)."""
     return _apply(x, fcblock, params, JACOBIAN, primal)
+
+
+def siren_hessian(x, fcblock, params=None, primal=None):
+    """d2y_c/dx_j dx_k per output channel, [..., out_features, in_features, in_features]
+    (diff_operators.hessian); in_features <= 3."""
+    return _apply(x, fcblock, params, HESSIAN, primal)
 
 
 def jacobian_of(x, weights, biases, w0, prec, batched):

@@ -7,6 +7,8 @@
   image_mse_log, image_mse_cubic, image_smape, image_asinh, image_perp, kspace_l1
                            loss_functions.py:12-64, 103-190 (the k-space loss family)
   ift_image_mse, image_l1  loss_functions.py:192-235
+  image_mse_TV_prior, image_mse_FH_prior  loss_functions.py:238-272 (the inpainting priors: the
+                           analytic gradient / Hessian at random coordinates)
   image_hypernetwork_{perp,asinh,l1,log,cubic,ift}_loss  loss_functions.py:295-323
   function_mse             loss_functions.py:326-327
   gradients_mse            loss_functions.py:330-335
@@ -27,6 +29,11 @@ mask applies when the image is 128x128 and the loss is the plain SSE otherwise.
 
 Deliberate deviation: image_mse_log does not print its two partial sums on every call
 (loss_functions.py:37); that print forces a host synchronisation per step.
+
+Deliberate deviation (in the style of bug 0.4): the two priors draw their random coordinates with
+torch.rand(shape) on the CPU default generator, as the reference does, and then move them to
+model_in's device instead of calling `.cuda()`: the random stream is the reference's, and the
+losses run on a CPU device too.
 """
 from __future__ import annotations
 
@@ -340,6 +347,40 @@ def image_l1(mask, model_output, gt):
     if mask is not None:
         diff = mask * diff
     return {"img_loss": diff.mean()}
+
+
+def _prior_coords(model_in):
+    """Half as many uniform random coordinates in [-1, 1) as model_in has rows
+    (loss_functions.py:239-241, 256-258): drawn on the CPU default generator, then moved."""
+    shape = (model_in.shape[0], model_in.shape[1] // 2, model_in.shape[2])
+    return (2 * (torch.rand(shape) - 0.5)).to(model_in.device)
+
+
+def _masked_image_mse(mask, model_output, gt):
+    sq = (model_output["model_out"] - gt["img"]) ** 2
+    if mask is not None:
+        sq = mask * sq
+    return sq.mean()
+
+
+def image_mse_TV_prior(mask, k1, model, model_output, gt):
+    """loss_functions.py:238-252: the masked image MSE plus k1 times the mean absolute gradient
+    of the model at random coordinates (total variation)."""
+    rand_output = model({"coords": _prior_coords(model_output["model_in"])})
+    g = diff_operators.gradient(rand_output["model_out"], rand_output["model_in"])
+    return {"img_loss": _masked_image_mse(mask, model_output, gt),
+            "prior_loss": k1 * torch.abs(g).mean()}
+
+
+def image_mse_FH_prior(mask, k1, model, model_output, gt):
+    """loss_functions.py:255-272: the masked image MSE plus k1 times the mean Frobenius norm of
+    the model's Hessian at random coordinates."""
+    rand_output = model({"coords": _prior_coords(model_output["model_in"])})
+    h, _ = diff_operators.hessian(rand_output["model_out"], rand_output["model_in"])
+    h = h.view(*h.shape[0:2], -1)
+    hessian_norm = h.norm(dim=-1, keepdim=True)
+    return {"img_loss": _masked_image_mse(mask, model_output, gt),
+            "prior_loss": k1 * torch.abs(hessian_norm).mean()}
 
 
 def image_hypernetwork_perp_loss(mask, kl, fw, model_output, gt):
