@@ -229,6 +229,17 @@ int siren_jvp_backward_ex(const siren_mlp_desc* d, int order, const float* x, co
                           const void* saved, int64_t saved_bytes, void* workspace, int64_t workspace_bytes,
                           float* const* dweight, float* const* dbias, float* dx, const void* primal,
                           int64_t primal_bytes, void* stream);
+/*
+ * The launch plans of siren_jvp_forward_ex and siren_jvp_backward_ex for this descriptor and order under
+ * the current options, as text (the contract of siren_mlp_backward_plan: at most cap bytes, the bytes
+ * needed are returned, -1 with siren_last_error set where the shape or a primal buffer is refused;
+ * no device is touched). flags: bit 0 an input gradient is wanted, bit 1 a primal buffer is given.
+ * After the line "# order=<o> prec=<fp32|bf16> flags=<f> streams=<1 + stored planes> fwd=<launches>
+ * bwd=<launches>", one line per launch, the forward pass (after its weight preparation) first:
+ *   <fwd|bwd> <kernel symbol with its template arguments> layer=<l> cur=<adjoint buffer holding the
+ *   layer's adjoints> grid=(x,y,z) block=<threads> [slab=part nsplit=<slabs written; reduce_kernel: summed>]
+ */
+int64_t siren_jvp_plan(const siren_mlp_desc* d, int order, int flags, char* out, int64_t cap);
 
 /*
  * Optional per-kernel-class timing, for benchmarks and profiling (not thread-safe; not for use

@@ -206,6 +206,7 @@ def _signatures():
         "siren_jvp_backward": (ci, [P, ci, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp]),
         "siren_jvp_forward_ex": (ci, [P, ci, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp]),
         "siren_jvp_backward_ex": (ci, [P, ci, vp, vp, vp, i64, vp, i64, pvp, pvp, vp, vp, i64, vp]),
+        "siren_jvp_plan": (i64, [P, ci, ci, cstr, i64]),
         "siren_timing_enable": (ci, [ci, ci]),
         "siren_timing_collect": (ci, [ctypes.POINTER(f64), pi64]),
         "siren_timing_disable": (None, []),

@@ -81,6 +81,20 @@ Split dw_ring_split(const Geo& g) {
   s.nsplit = std::max<int64_t>(1, cdiv(g.rows, s.rows_per_split));
   return s;
 }
+// jvp_tn2_kernel (fp32 weight gradient of a hidden layer, here and in rt_jvp.hip): all 256 dW rows (the
+// layer's width M) per workgroup over `stacked_rows` rows; option jvp_tn2 (default on). Its input width N
+// must be a multiple of 4, which a hidden width (a multiple of 32, siren_mlp_check) always is.
+bool jvp_tn2_ok(int M, int N) {
+  assert(N % 4 == 0);
+  return g_jvp_tn2 && M == 256;
+}
+Split jtn2_split(const Geo& g, int64_t stacked_rows, int N) {
+  const int64_t want = std::max<int64_t>(1, 256 / (cdiv(N, JTN2_BN) * g.nb));
+  Split s;
+  s.rows_per_split = std::max<int64_t>(JTN2_KC, align_up(cdiv(stacked_rows, want), JTN2_KC));
+  s.nsplit = std::max<int64_t>(1, cdiv(stacked_rows, s.rows_per_split));
+  return s;
+}
 
 // Distance between consecutive split slabs (all weight sets of one split), padded to float4.
 int64_t split_stride(const Geo& g, int64_t slab) { return align_up(g.nb * slab, 4); }
@@ -97,10 +111,6 @@ int64_t pair_count(const Geo& g) {
   const int64_t np = std::max<int64_t>(8, (kMaxPairs / g.nb) / 8 * 8);
   return std::min<int64_t>(np, align_up(ntiles, 8));
 }
-
-// rt_jvp.hip's all-rows weight-gradient tile, which the fp32 backward and its workspace size use too
-Split jtn2_split(const Geo& g, int64_t stacked_rows, int N);
-bool jvp_tn2_ok(int M, int N);
 
 struct Layout {
   // saved
@@ -930,6 +940,15 @@ std::string plan_text(const BwdPlan& p) {
     t += buf;
   }
   return t;
+}
+// A plan text into the caller's buffer, cut to fit and terminated; returns the bytes the whole text needs.
+int64_t text_out(const std::string& t, char* out, int64_t cap) {
+  if (out && cap > 0) {
+    const size_t n = std::min<size_t>(t.size(), (size_t)cap - 1);
+    memcpy(out, t.data(), n);
+    out[n] = 0;
+  }
+  return (int64_t)t.size() + 1;
 }
 
 // One backward call's buffers, and the launcher of every kind of plan step.

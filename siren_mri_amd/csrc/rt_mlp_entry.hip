@@ -165,13 +165,7 @@ int64_t siren_mlp_backward_plan(const siren_mlp_desc* d, int flags, char* out, i
   if (d->ff_B && (flags & 1)) return fail(SIREN_EINVAL, "fourier input: no input gradient (dx must be NULL)"), -1;
   const BwdPlan p = plan_backward(d, geo_of(d), layout_of(d), flags & 1, flags & 2, flags & 4);
   if (p.error) return fail(SIREN_EINVAL, "%s", p.error), -1;
-  const std::string t = plan_text(p);
-  if (out && cap > 0) {
-    const size_t n = std::min<size_t>(t.size(), (size_t)cap - 1);
-    memcpy(out, t.data(), n);
-    out[n] = 0;
-  }
-  return (int64_t)t.size() + 1;
+  return text_out(plan_text(p), out, cap);
 }
 
 }  // extern "C"
