@@ -95,6 +95,27 @@ int siren_mlp64_backward(const siren_mlp_desc* d, const double* x, const double*
                          int64_t saved_bytes, void* workspace, int64_t workspace_bytes, double* const* dW,
                          double* const* db, double* dx, void* stream);
 
+/*
+ * Buffers — what holds for every entry point of this header:
+ *  - Nothing outside the buffers a call is given is written: every operand is exactly its documented
+ *    shape, `saved` and `workspace` exactly the bytes their *_bytes() query returns. A buffer shorter
+ *    than that is refused with SIREN_ENOSPACE before anything is launched.
+ *  - Bytes outside those buffers never affect a result (they may be NaN).
+ *  - `workspace` may hold anything on entry and holds nothing of value on return. The exceptions are
+ *    the three zeroed-once workspaces: siren_sse_workspace_bytes() (every loss forward, and
+ *    siren_loss_desc.loss_workspace), siren_sumsq_workspace_bytes(), and the ticket word of
+ *    siren_enc_workspace_bytes() (at byte siren_enc_workspace_bytes() - 256; the partial sums in front
+ *    of it are scratch). The caller zero-fills them once; every launch leaves them zeroed.
+ *  - `saved` (and `primal`) is read-only in a backward; inputs are never written. The operands
+ *    documented as updated in place are siren_enc_bias_relu's y, siren_adam_step's param / exp_avg /
+ *    exp_avg_sq / dev_steps and the step counter t of siren_adam_scalars*.
+ *  - Operands need only the alignment of their element type. The exceptions: the weights of the hidden
+ *    layers 1 .. L-2 of a siren_mlp_desc must be 16-byte aligned (siren_mlp_check); bf16 encoder planes
+ *    and filters are 16-byte aligned (rows of C >= 8 channels). A 16-byte aligned x or dy only selects
+ *    faster forms of the same arithmetic (siren_mlp_backward_plan's flags).
+ * tests/test_gpu_arena_*.py hold every entry point to this on buffers carved from NaN-filled memory.
+ */
+
 /* Bytes of the per-call "saved" buffer (the activations kept between forward and
  * backward: one phase tensor per sine layer). */
 int64_t siren_mlp_saved_bytes(const siren_mlp_desc* d);

@@ -3,10 +3,11 @@
 // siren_runtime.hip.
 namespace {
 
-// The hand-off workspace of a loss forward, checked and sliced; 0 or SIREN_EINVAL (message set).
+// The hand-off workspace of a loss forward, checked and sliced; 0 or SIREN_ENOSPACE (message set), as
+// every other entry point answers a missing or short workspace (check_buffers).
 int loss_slots(const char* what, void* workspace, int64_t ws_bytes, float** partial, unsigned** counter) {
   if (!workspace || ws_bytes < siren_sse_workspace_bytes())
-    return fail(SIREN_EINVAL, "%s: workspace of %lld bytes, need %lld", what, (long long)ws_bytes,
+    return fail(SIREN_ENOSPACE, "%s: workspace of %lld bytes, need %lld", what, (long long)ws_bytes,
                 (long long)siren_sse_workspace_bytes());
   loss_workspace_slice(workspace, partial, counter);
   return SIREN_OK;

@@ -220,7 +220,8 @@ constexpr int KSPACE_MAXC = 8;
 //             compiler cannot drop it), then takes a ticket with one agent-scope atomic add;
 //   consumer: the workgroup whose add returned the workgroup count - 1 reads every sum with sc1
 //             loads (relaxed agent-scope loads = global_load sc1, served from L2, never from a stale
-//             L1), then stores 0 to the counter: it is zero between launches.
+//             L1) and stores 0 back to each slot it has read (handoff_take), then stores 0 to the
+//             counter: the whole workspace is zero between launches, as the header promises.
 // This avoids the L2 write-back / invalidate of acq_rel fences (several us per launch). The
 // slots/counter workspace is per (device, stream) on the host side, so two launches never share it
 // concurrently.
@@ -231,6 +232,11 @@ DEV unsigned handoff_publish(float* slot, float s, unsigned* counter) {
 }
 DEV float handoff_read(const float* slot) {
   return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+DEV float handoff_take(float* slot) {
+  const float v = handoff_read(slot);
+  __hip_atomic_store(slot, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return v;
 }
 DEV void handoff_rearm(unsigned* counter) {
   __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -256,7 +262,7 @@ DEV void block_sum_handoff(float acc, float* partial, unsigned* counter, unsigne
   __syncthreads();
   if (ticket != nwg - 1) return;
   float s = 0.f;
-  for (unsigned b = threadIdx.x; b < nwg; b += WAVES * 64) s += handoff_read(partial + b);
+  for (unsigned b = threadIdx.x; b < nwg; b += WAVES * 64) s += handoff_take(partial + b);
   s = wave_sum(s);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;

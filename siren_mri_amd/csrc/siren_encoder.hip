@@ -465,7 +465,7 @@ __global__ __launch_bounds__(256) void sumsq_fwd_kernel(SumsqArgs a) {
   if (!last) return;
   // the last block: thread t adds partials t, t + 256, ... in order, then the same LDS tree
   float s = 0.f;
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) s += handoff_read(a.part + b);
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) s += handoff_take(a.part + b);
   red[threadIdx.x] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {

@@ -890,7 +890,7 @@ __global__ __launch_bounds__(512) void fused_fwd_reg_kernel(FwdRegArgs a) {
     __syncthreads();
     if (lticket == nwg - 1) {
       float sacc = 0.f;
-      for (unsigned b = tid; b < nwg; b += 512) sacc += __hip_atomic_load(a.lpart + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (unsigned b = tid; b < nwg; b += 512) sacc += handoff_take(a.lpart + b);  // (the slot goes back to zero)
       sacc = wave_sum(sacc);
       __syncthreads();
       if (lane == 0) lred[wave] = sacc;

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(KfGeom<L>::T) void kift_fwd_kernel(KiftArgs a) {
   __syncthreads();
   if (ticket != gridDim.x - 1) return;
   // the last workgroup: the slice sums in slice order
-  for (unsigned b = threadIdx.x; b < gridDim.x; b += G::T) slots[b] = handoff_read(a.partial + b);
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += G::T) slots[b] = handoff_take(a.partial + b);
   __syncthreads();
   if (threadIdx.x == 0) {
     float tot = 0.f;

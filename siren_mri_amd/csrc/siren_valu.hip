@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void last_fwd_kernel(LastFwdArgs a) {
     __syncthreads();
     if (lticket == nwg - 1) {
       float sacc = 0.f;
-      for (unsigned b = tid; b < nwg; b += 256) sacc += handoff_read(a.lpart + b);
+      for (unsigned b = tid; b < nwg; b += 256) sacc += handoff_take(a.lpart + b);
       sacc = wave_sum(sacc);
       __syncthreads();
       if (lane == 0) lred[wave] = sacc;

@@ -87,7 +87,7 @@ def test_entry_points_reject_bad_arguments(which):
 
 def test_forward_rejects_short_workspace():
     lib = _native.load_library()
-    assert _call(lib, "ift_loss_forward", ws_bytes=int(lib.siren_sse_workspace_bytes()) - 1) == -1
+    assert _call(lib, "ift_loss_forward", ws_bytes=int(lib.siren_sse_workspace_bytes()) - 1) == -3  # ENOSPACE
     err = _native.last_error()
     assert "workspace" in err and "kspace_ift_loss_forward" in err
     assert loss_functions._kift_max_batch() == _slots(lib) == 1024

@@ -150,7 +150,7 @@ def test_entry_points_reject_bad_arguments(which):
 
 def test_forward_rejects_small_workspace():
     lib = _native.load_library()
-    assert _call(lib, "forward", _native.KLOSS_L1, 2, ws_bytes=int(lib.siren_sse_workspace_bytes()) - 1) == -1
+    assert _call(lib, "forward", _native.KLOSS_L1, 2, ws_bytes=int(lib.siren_sse_workspace_bytes()) - 1) == -3  # ENOSPACE
     assert "workspace" in _native.last_error()
 
 
