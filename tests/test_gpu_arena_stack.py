@@ -40,13 +40,14 @@ U8 = torch.uint8
 
 
 @functools.lru_cache(maxsize=None)
-def problem(prec, dims, sets, rows, outermost_linear=True):
-    """Parameters, x and dy of one shape (CPU fp32), and the fp64 oracle's y, gradients and dx."""
+def problem(prec, dims, sets, rows, outermost_linear=True, seed=0):
+    """Parameters, x and dy of one shape (CPU fp32), and the fp64 oracle's y, gradients and dx. seed:
+    another draw of the same shape (tests/test_gpu_rows_stack.py; 0 is the draw of this file's tests)."""
     dims = list(dims)
-    g = torch.Generator().manual_seed(1000 * len(dims) + 7 * rows + sets + dims[0])
+    g = torch.Generator().manual_seed(1000 * len(dims) + 7 * rows + sets + dims[0] + 100003 * seed)
     params = []
     for l in range(len(dims) - 1):
-        W, b = orc.siren_init(dims, seed=rows + l)[l]
+        W, b = orc.siren_init(dims, seed=rows + l + 1009 * seed)[l]
         if sets:
             W = W.unsqueeze(0).repeat(sets, 1, 1) * (1 + 0.1 * torch.randn(sets, 1, 1, generator=g))
             b = b.unsqueeze(0).repeat(sets, 1) + 0.01 * torch.randn(sets, dims[l + 1], generator=g)
