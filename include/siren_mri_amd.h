@@ -355,7 +355,9 @@ int64_t siren_enc_workspace_bytes(void);
 int64_t siren_conv_wrw_workspace_bytes(int N, int H, int W);
 /* Forward convolution of the same shape, bf16 NHWC x [N][H][128][128] (H even) and filter w
  * [128 out][5][5][128 in] (channels-last) -> bf16 y, fp32 accumulation; with bias ([128] bf16)
- * y = bf16(bf16(acc) + bias) (then ReLU if relu), the rounding of the conv + bias-add chain. The
+ * y = bf16(bf16(acc) + bias) (then ReLU if relu), the rounding of the conv + bias-add chain;
+ * without a bias y = bf16(acc). The ReLU is part of the bias epilogue: relu != 0 with a NULL bias is
+ * refused with SIREN_EINVAL before any launch (siren_conv_fwd likewise). The
  * input gradient of such a convolution is this one on the flipped, transposed filter. Replaces
  * the encoder's MIOpen forward / input-gradient convolutions for this shape. */
 int siren_conv_fwd_k5(const void* x, const void* w, const void* bias, int relu, void* y, int N, int H, int W, int C,
@@ -385,7 +387,8 @@ int siren_conv_wrw_k5(const void* x, const void* dy, int N, int H, int W, int C,
  * transposed filter, and the 3x3 forms), stride 1, 'same' padding, bf16 NHWC, fp32 accumulation:
  * filter size KS in {3, 5, 7}, CI in {2, 64, 128} input channels (2: conv_theta over the real /
  * imaginary k-space image, modules.py:359).
- *   siren_conv_fwd : y = conv(x, w) (+ bias, ReLU as siren_conv_fwd_k5); W = 128; CI 64/128: H
+ *   siren_conv_fwd : y = conv(x, w) (+ bias, ReLU as siren_conv_fwd_k5: relu != 0 needs a bias,
+ *                    SIREN_EINVAL otherwise); W = 128; CI 64/128: H
  *                    even, CO a multiple of 64; CI 2: CO in {32, 64, 96, 128}; w is [CO][KS][KS][CI].
  *   siren_conv_wrw : dw[CO][KS][KS][CI] (fp32) = the weight gradient of that convolution; CI 64/128:
  *                    W a multiple of 64, CO a multiple of 128 (CI 64) or 64 (CI 128); CI 2: W a

@@ -128,6 +128,7 @@ int siren_conv_fwd_k5(const void* x, const void* w, const void* bias, int relu, 
     return fail(SIREN_EINVAL, "conv_fwd_k5: needs C = %d, W = %d and H even (C = %d, N = %d, H = %d, W = %d)", CW_C,
                 CF_W, C, N, H, W);
   if (!x || !w || !y) return fail(SIREN_EINVAL, "conv_fwd_k5: null pointer");
+  if (relu && !bias) return fail(SIREN_EINVAL, "conv_fwd_k5: relu needs a bias (the ReLU is part of the bias epilogue)");
   ConvFArgs a;
   memset(&a, 0, sizeof(a));
   a.x = (const bf16*)x;
@@ -208,6 +209,7 @@ int siren_conv_fwd(const void* x, const void* w, const void* bias, int relu, voi
   int rc = conv_shape_check(0, N, H, W, CI, CO, KS);
   if (rc) return rc;
   if (!x || !w || !y) return fail(SIREN_EINVAL, "conv fwd: null pointer");
+  if (relu && !bias) return fail(SIREN_EINVAL, "conv fwd: relu needs a bias (the ReLU is part of the bias epilogue)");
   ConvGArgs a;
   memset(&a, 0, sizeof(a));
   a.x = (const bf16*)x;

@@ -120,8 +120,10 @@ def _conv(x, wb, bb, pad, relu=False):
     """Stride-1 'same' convolution, bf16 NHWC out: the native MFMA kernels — the residual blocks'
     128 -> 128 5x5 shape (siren_conv_fwd_k5), the other 3x3 / 5x5 / 7x7 shapes with 2, 64 or 128
     input channels (siren_conv_fwd: conv_theta, cnn[0] and its input gradient), bias + ReLU in
-    their epilogue — and MIOpen for the rest (the 1x1, other widths; relu=True needs a bias on that
-    path and is applied by siren_enc_bias_relu)."""
+    their epilogue — and MIOpen for the rest (the 1x1, other widths; there relu=True is applied by
+    siren_enc_bias_relu). relu=True needs a bias on every path: the native entry points refuse it
+    without one (SIREN_EINVAL), and every caller passes the convolution's own."""
+    assert bb is not None or not relu, "relu=True needs a bias"
     if _native_conv(x, wb):
         n, _, h, w = x.shape
         y = torch.empty((n, wb.shape[0], h, w), dtype=torch.bfloat16, device=x.device, memory_format=_CL)

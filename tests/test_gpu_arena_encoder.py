@@ -8,7 +8,8 @@ Each driver runs on ordinary zero-filled buffers and on the arena; after the are
 sum-of-squares workspace are zero again) hold, and I5 every output is bit-equal to the plain run (all of
 these sum in fixed orders: test_native_passes_deterministic, the run-to-run assertions of
 test_gpu_encoder.py, test_native_heads_deterministic, test_hypo_weight_loss_native_sum_of_squares). I7: a
-workspace one byte short is refused with SIREN_ENOSPACE before any launch. The arena run is also compared
+workspace one byte short is refused with SIREN_ENOSPACE before any launch, and a forward convolution
+asked for a ReLU without a bias with SIREN_EINVAL. The arena run is also compared
 with torch on the same operands, at the bounds of test_gpu_encoder.py / test_gpu_hyper.py /
 test_gpu_optim.py, so the two runs cannot be wrong together; the fused convolution epilogues
 (siren_conv_fwd_k5_res, siren_conv_dgrad_k5_fused) are compared with the separate passes bit for bit, as
@@ -29,6 +30,7 @@ from siren_mri_amd import _native  # noqa: E402
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 ENOSPACE = -3
+EINVAL = -1
 F32, BF16, U8, F64 = torch.float32, torch.bfloat16, torch.uint8, torch.float64
 
 
@@ -233,12 +235,15 @@ def conv_inputs(N, H, W, ci, co, k, seed=0):
     return x, w, torch.randn(co, generator=g).to(BF16), torch.randn(N, co, H, W, generator=g).to(BF16)
 
 
-def run_conv_fwd(alloc, ci, co, k, bias, relu, k5):
+def run_conv_fwd(alloc, ci, co, k, bias, relu, k5, refuse=False):
     lib = _native.lib()
     N, H = (2, 5) if ci == 2 else (2, 6)
     x, w, b, _ = conv_inputs(N, H, 128, ci, co, k)
     xd, wd, bd = inp(alloc, "x", nhwc(x)), inp(alloc, "w", nhwc(w)), inp(alloc, "bias", b)
     o = {"y": alloc.take((N, H, 128, co), BF16, role="output", name="y")}
+    if refuse:  # relu without a bias: the ReLU lives in the bias epilogue, so the call is refused
+        return (lib.siren_conv_fwd_k5(ptr(xd), ptr(wd), None, 1, ptr(o["y"]), N, H, 128, 128, stream()) if k5 else
+                lib.siren_conv_fwd(ptr(xd), ptr(wd), None, 1, ptr(o["y"]), N, H, 128, ci, co, k, stream()))
     if k5:
         ok(lib.siren_conv_fwd_k5(ptr(xd), ptr(wd), ptr(bd) if bias else None, int(relu), ptr(o["y"]), N, H, 128, 128, stream()))
     else:
@@ -263,6 +268,18 @@ def test_conv_forward(ci, co, k, k5, bias, relu, dma):
     got = o["y"].cpu().permute(0, 3, 1, 2).float()
     assert orc.norm_rel(got, ref.float()) < 4e-3  # test_gpu_encoder.py: at most one bf16 rounding step apart
     assert ((got - ref.float()).abs() <= ref.float().abs() * 2 ** -7 + 1e-6).float().mean() > 0.999
+
+
+@pytest.mark.parametrize("ci,co,k,k5", [(128, 128, 5, True), (128, 128, 5, False), (64, 128, 7, False), (2, 64, 7, False)])
+def test_conv_forward_relu_without_bias_is_refused_before_any_launch(ci, co, k, k5):
+    """include/siren_mri_amd.h: relu != 0 with a NULL bias is SIREN_EINVAL (the kernels would skip the
+    ReLU silently), with a last_error text and nothing launched."""
+    plain = Plain(DEV)
+    run_conv_fwd(plain, ci, co, k, True, True, k5)
+    arena = plain.arena()
+    assert run_conv_fwd(arena, ci, co, k, False, True, k5, refuse=True) == EINVAL
+    assert "relu needs a bias" in _native.last_error()
+    arena.assert_nothing_launched()
 
 
 def res_inputs():
