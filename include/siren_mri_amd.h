@@ -594,6 +594,36 @@ int siren_kspace_ift_loss_backward(const siren_kift_desc* desc, const float* pre
                                    void* stream);
 
 /*
+ * The signed-distance fitting loss (siren_sdf.hip; replaces loss_functions.sdf, loss_functions.py:460-484)
+ * on the rows of a one-output model and of its input gradient. All operands float32, contiguous:
+ *   pred, sdf [rows]        model output; ground truth: a row is on the surface iff sdf != -1 (exact)
+ *   grad, nrm [rows, dims]  diff_operators.gradient(pred, coords); ground-truth normals; dims 2 or 3
+ * siren_sdf_loss_forward   out4 (device) = the reference's four terms, each a mean over the rows with
+ *                    its constant folded in, in the order of the reference's dict:
+ *                      [0] sdf                3e3 / rows sum  on ? |pred| : 0
+ *                      [1] inter              1e2 / rows sum  on ? 0 : exp(-1e2 |pred|)
+ *                      [2] normal_constraint  1e2 / rows sum  on ? 1 - cos(grad, nrm) : 0
+ *                      [3] grad_constraint    5e1 / rows sum  | |grad| - 1 |
+ *                    cos = sum_k (g_k / max(|g|, 1e-8)) (n_k / max(|n|, 1e-8)) (F.cosine_similarity). The
+ *                    branch a row does not select is not evaluated: the normals of an off-surface row
+ *                    (NaN included) reach no result. One launch, deterministic summation order (four
+ *                    sums behind one hand-off ticket, at most 256 workgroups); workspace as
+ *                    siren_sse_forward's (siren_sse_workspace_bytes()). Nothing is kept for the
+ *                    backward. rows == 0: four zeros.
+ * siren_sdf_loss_backward  dpred [rows], dgrad [rows, dims] = d(sum_k g4[k] out4[k]) / d(pred, grad),
+ *                    recomputed from the four inputs in one launch; g4 is a device 4-vector. At zero
+ *                    the gradients are torch autograd's: sign(0) = 0, d|g|/dg = 0 at g = 0,
+ *                    d max(|g|, eps)/d|g| = 1 iff |g| >= eps; pred == 0 and |g| == 1 give exactly 0.
+ *                    rows == 0: nothing is launched.
+ * SIREN_EINVAL for dims outside {2, 3} or a null pointer with rows > 0; SIREN_ENOSPACE for a missing or
+ * short workspace, as every loss forward.
+ */
+int siren_sdf_loss_forward(const float* pred, const float* grad, const float* sdf, const float* nrm, int64_t rows,
+                           int dims, float* out4, void* workspace, int64_t ws_bytes, void* stream);
+int siren_sdf_loss_backward(const float* pred, const float* grad, const float* sdf, const float* nrm, int64_t rows,
+                            int dims, const float* g4, float* dpred, float* dgrad, void* stream);
+
+/*
  * Gaussian Fourier features (replaces GaussianFourierFeatureTransform.forward, features.py:31-41):
  * out [rows, 2 m] = cat(sin(2 pi x B), cos(2 pi x B)) for x [rows, cin], B [cin, m] (device float32),
  * one launch. Feeds the SIREN's wide first layer (5..16 inputs on the register-resident forward).

@@ -1,6 +1,6 @@
 // rt_loss.hip — image and k-space losses, data consistency, Fourier features and the sin/cos probe
-// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_kfft.hip). Included by
-// siren_runtime.hip.
+// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_sdf.hip, siren_kfft.hip). Included
+// by siren_runtime.hip.
 namespace {
 
 // The hand-off workspace of a loss forward, checked and sliced; 0 or SIREN_ENOSPACE (message set), as
@@ -54,6 +54,33 @@ KlossArgs kloss_args(const siren_kloss_desc* d, const float* pred, const float* 
   a.divisor = d->divisor;
   a.mag_weight = d->mag_weight;
   a.phase_weight = d->phase_weight;
+  return a;
+}
+
+// the forms of the signed-distance loss kernels, by D - 2 (dims checked by sdf_check)
+const Kernel<SdfArgs> kSdfFwd[2] = {SIREN_K(sdf_fwd_kernel<2>), SIREN_K(sdf_fwd_kernel<3>)};
+const Kernel<SdfArgs> kSdfBwd[2] = {SIREN_K(sdf_bwd_kernel<2>), SIREN_K(sdf_bwd_kernel<3>)};
+
+// the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
+int sdf_check(const char* what, const float* pred, const float* grad, const float* sdf, const float* nrm,
+              int64_t rows, int dims) {
+  if (dims != 2 && dims != 3) return fail(SIREN_EINVAL, "%s: dims %d is neither 2 nor 3", what, dims);
+  if (rows < 0) return fail(SIREN_EINVAL, "%s: bad size (rows=%lld)", what, (long long)rows);
+  if (rows > 0 && (!pred || !grad || !sdf || !nrm)) return fail(SIREN_EINVAL, "%s: null pointer", what);
+  return SIREN_OK;
+}
+
+// the reference's constants (loss_functions.py:481-484) over the row count: each term is a mean
+SdfArgs sdf_args(const float* pred, const float* grad, const float* sdf, const float* nrm, int64_t rows) {
+  SdfArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.grad = grad;
+  a.sdf = sdf;
+  a.nrm = nrm;
+  a.rows = rows;
+  const double c[SDF_TERMS] = {3e3, 1e2, 1e2, 5e1};
+  for (int k = 0; k < SDF_TERMS; ++k) a.w[k] = rows > 0 ? (float)(c[k] / (double)rows) : 0.f;
   return a;
 }
 
@@ -228,6 +255,32 @@ int siren_kspace_loss_backward(int kind, const siren_kloss_desc* desc, const flo
   a.out = dpred;
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(batch * npix, KL_THREADS)));
   return launch_kernel(kKlossBwd[kind], dim3(blocks), KL_THREADS, 0, "kspace_loss_backward", (hipStream_t)stream, a);
+}
+
+int siren_sdf_loss_forward(const float* pred, const float* grad, const float* sdf, const float* nrm, int64_t rows,
+                           int dims, float* out4, void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = sdf_check("sdf_loss_forward", pred, grad, sdf, nrm, rows, dims)) return rc;
+  if (!out4) return fail(SIREN_EINVAL, "sdf_loss_forward: null pointer");
+  SdfArgs a = sdf_args(pred, grad, sdf, nrm, rows);
+  if (int rc = loss_slots("sdf_loss_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
+  a.out = out4;
+  // one row per thread per iteration; four slots per workgroup, so at most LOSS_SLOTS / 4 = 256 of them
+  // (rows == 0: one workgroup writes the four zeros)
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(SDF_MAX_BLOCKS, cdiv(rows, SDF_THREADS)));
+  return launch_kernel(kSdfFwd[dims - 2], dim3(blocks), SDF_THREADS, 0, "sdf_loss_forward", (hipStream_t)stream, a);
+}
+
+int siren_sdf_loss_backward(const float* pred, const float* grad, const float* sdf, const float* nrm, int64_t rows,
+                            int dims, const float* g4, float* dpred, float* dgrad, void* stream) {
+  if (int rc = sdf_check("sdf_loss_backward", pred, grad, sdf, nrm, rows, dims)) return rc;
+  if (rows > 0 && (!g4 || !dpred || !dgrad)) return fail(SIREN_EINVAL, "sdf_loss_backward: null pointer");
+  if (rows == 0) return SIREN_OK;
+  SdfArgs a = sdf_args(pred, grad, sdf, nrm, rows);
+  a.g = g4;
+  a.dpred = dpred;
+  a.dgrad = dgrad;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(rows, SDF_THREADS)));
+  return launch_kernel(kSdfBwd[dims - 2], dim3(blocks), SDF_THREADS, 0, "sdf_loss_backward", (hipStream_t)stream, a);
 }
 
 int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream) {

@@ -276,6 +276,60 @@ DEV void block_sum_handoff(float acc, float* partial, unsigned* counter, unsigne
   }
 }
 
+// The K-wide sibling: K sums per workgroup behind ONE ticket (a second block_sum_handoff on the same
+// counter would not do: workgroups that have finished the first call would race the second's ticket).
+// Sum k of workgroup wg goes to slot k nwg + wg, so at most LOSS_SLOTS / K workgroups; all K stores are
+// drained by the one s_waitcnt before the ticket is taken. In the last workgroup thread t adds slots
+// k nwg + t, k nwg + t + 64 WAVES, ... in order, then the same tree, and out[k] = total_k * weight[k].
+template <int WAVES, int K>
+DEV void block_sums_handoff(const float (&acc)[K], float* partial, unsigned* counter, unsigned wg, unsigned nwg,
+                            float* out, const float (&weight)[K]) {
+  __shared__ float red[K][WAVES];
+  __shared__ unsigned ticket;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float s = wave_sum(acc[k]);
+    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) s += red[k][w];
+      __hip_atomic_store(partial + (size_t)k * nwg + wg, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (ticket != nwg - 1) return;
+  float tot[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float s = 0.f;
+    for (unsigned b = threadIdx.x; b < nwg; b += WAVES * 64) s += handoff_take(partial + (size_t)k * nwg + b);
+    tot[k] = wave_sum(s);
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][threadIdx.x >> 6] = tot[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float t = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) t += red[k][w];
+      out[k] = t * weight[k];
+    }
+    handoff_rearm(counter);
+  }
+}
+
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // ds_read_b64_tr_b16: lane (4q+p) of each 16-lane group supplies the address of row q,

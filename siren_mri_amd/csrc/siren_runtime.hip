@@ -20,6 +20,7 @@
 #include "siren_loss.hip"
 #include "siren_kspace.hip"
 #include "siren_kloss.hip"
+#include "siren_sdf.hip"
 #include "siren_kfft.hip"
 #include "siren_encoder.hip"
 #include "siren_conv.hip"

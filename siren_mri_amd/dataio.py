@@ -9,6 +9,8 @@ Restated from the reference:
                                                 laplace ground truth via scipy.ndimage)
   ImageGeneralizationWrapper dataio.py:861-986 (CS-Cartesian masks, conv_cnp inputs)
   FastMRIBrainKspace layout  dataio.py:585-664 (fftshift(fft2(slice)) stacked [H, W, 2])
+  PointCloud                 dataio.py:401-453 (oriented point cloud -> on- / off-surface SDF batches;
+                                                write_synthetic_point_cloud writes an analytic one)
 
 Deviation (bug 0.7): fastMRI .h5 volumes are not available, so
 SyntheticMRIKspace produces k-space of seeded phantoms with the same [H, W, 2] float32 layout:
@@ -297,3 +299,73 @@ class ImageGeneralizationWrapper(Dataset):
         in_dict = {k: v.to(self.device) for k, v in in_dict.items()}
         gt = {k: v.to(self.device) for k, v in gt.items()}
         return in_dict, gt
+
+
+class PointCloud(Dataset):
+    """An oriented point cloud as signed-distance training batches (dataio.py:401-453): the file holds
+    `x y z nx ny nz` rows (np.genfromtxt); the points are centred on their mean and scaled to [-1, 1] by
+    the global min/max (keep_aspect_ratio) or per axis. An item is on_surface_points random surface
+    points (sdf 0, their normals) followed by as many uniform points of the cube (sdf -1, normals -1),
+    drawn from the global numpy generator: np.random.choice, then np.random.uniform."""
+
+    def __init__(self, pointcloud_path, on_surface_points, keep_aspect_ratio=True):
+        super().__init__()
+        point_cloud = np.genfromtxt(pointcloud_path)
+        coords = point_cloud[:, :3]
+        self.normals = point_cloud[:, 3:]
+        coords -= np.mean(coords, axis=0, keepdims=True)
+        if keep_aspect_ratio:
+            coord_max, coord_min = np.amax(coords), np.amin(coords)
+        else:
+            coord_max = np.amax(coords, axis=0, keepdims=True)
+            coord_min = np.amin(coords, axis=0, keepdims=True)
+        self.coords = (coords - coord_min) / (coord_max - coord_min)
+        self.coords -= 0.5
+        self.coords *= 2.0
+        self.on_surface_points = on_surface_points
+
+    def __len__(self):
+        return self.coords.shape[0] // self.on_surface_points
+
+    def __getitem__(self, idx):
+        n_on = n_off = self.on_surface_points
+        rand_idcs = np.random.choice(self.coords.shape[0], size=n_on)
+        off_surface_coords = np.random.uniform(-1, 1, size=(n_off, 3))
+        sdf = np.zeros((n_on + n_off, 1))
+        sdf[n_on:, :] = -1
+        coords = np.concatenate((self.coords[rand_idcs, :], off_surface_coords), axis=0)
+        normals = np.concatenate((self.normals[rand_idcs, :], np.ones((n_off, 3)) * -1), axis=0)
+        return ({"coords": torch.from_numpy(coords).float()},
+                {"sdf": torch.from_numpy(sdf).float(), "normals": torch.from_numpy(normals).float()})
+
+
+TORUS_RADII = (0.6, 0.25)  # write_synthetic_point_cloud's torus: centre-line and tube radius
+SPHERE_RADIUS = 0.6
+
+
+def write_synthetic_point_cloud(path, shape="torus", n=20000, seed=0):
+    """Write an analytic oriented point cloud as `x y z nx ny nz` text rows (.xyz), the input of
+    PointCloud: n points uniform by area on the torus (sqrt(x^2 + y^2) - R)^2 + z^2 = r^2 with
+    (R, r) = TORUS_RADII (the tube angle v by rejection against the area density R + r cos v), or on the
+    sphere of SPHERE_RADIUS, with their exact outward unit normals. Returns the [n, 6] float64 array."""
+    rs = np.random.RandomState(seed)
+    if shape == "sphere":
+        nrm = rs.standard_normal((n, 3))
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        pts = SPHERE_RADIUS * nrm
+    elif shape == "torus":
+        R, r = TORUS_RADII
+        v = np.empty(0)
+        while v.size < n:
+            cand = rs.uniform(0.0, 2 * np.pi, size=2 * n)
+            keep = rs.uniform(0.0, R + r, size=2 * n) < R + r * np.cos(cand)
+            v = np.concatenate((v, cand[keep]))
+        v = v[:n]
+        u = rs.uniform(0.0, 2 * np.pi, size=n)
+        nrm = np.stack((np.cos(v) * np.cos(u), np.cos(v) * np.sin(u), np.sin(v)), axis=1)
+        pts = np.stack((R * np.cos(u), R * np.sin(u), np.zeros(n)), axis=1) + r * nrm
+    else:
+        raise ValueError(f"unknown shape {shape!r}; 'torus' or 'sphere'")
+    cloud = np.concatenate((pts, nrm), axis=1)
+    np.savetxt(path, cloud, fmt="%.12f")
+    return cloud

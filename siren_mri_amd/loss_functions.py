@@ -13,6 +13,8 @@
   function_mse             loss_functions.py:326-327
   gradients_mse            loss_functions.py:330-335
   laplace_mse              loss_functions.py:350-355
+  sdf                      loss_functions.py:460-484 (signed-distance fitting: four terms on the
+                           output and its analytic gradient; siren_mri_amd::sdf_loss, siren_sdf.hip)
 
 image_mse runs on the native k-space op (siren_kspace.hip), with the data consistency of a native
 DataConsistencyInKspace output folded in. The six k-space losses of the
@@ -432,3 +434,61 @@ def gradients_mse(model_output, gt):
 def laplace_mse(model_output, gt):
     lap = diff_operators.laplace(model_output["model_out"], model_output["model_in"])
     return {"laplace_loss": torch.mean((lap - gt["laplace"]) ** 2)}
+
+
+_SDF_NATIVE = True
+_SDF_KEYS = ("sdf", "inter", "normal_constraint", "grad_constraint")
+
+
+def set_sdf_loss_native(enabled: bool) -> None:
+    """Run sdf on the native op where it applies (default on); off: the reference's expression in
+    PyTorch everywhere (A/B tests)."""
+    global _SDF_NATIVE
+    _SDF_NATIVE = bool(enabled)
+
+
+def _sdf_native_applies(pred, gradient, gt_sdf, gt_normals):
+    """Whether sdf of these operands runs on siren_mri_amd::sdf_loss: float32 [B, N, 1] / [B, N, D] on
+    one GPU, D 2 or 3, ground truth that needs no gradient."""
+    if not (_SDF_NATIVE and pred.is_cuda and pred.dim() == 3 and pred.shape[-1] == 1 and gradient.dim() == 3
+            and gradient.shape[-1] in (2, 3) and gradient.shape[:2] == pred.shape[:2]):
+        return False
+    if gt_sdf.shape != pred.shape or gt_normals.shape != gradient.shape:
+        return False
+    return all(t.dtype == torch.float32 and t.device == pred.device for t in (pred, gradient, gt_sdf, gt_normals)) \
+        and not (gt_sdf.requires_grad or gt_normals.requires_grad)
+
+
+def sdf(model_output, gt):
+    """loss_functions.py:460-484: the four terms of signed-distance fitting on a batch of on-surface
+    (gt sdf != -1) and off-surface (gt sdf == -1) points: |y| on the surface, exp(-1e2 |y|) off it,
+    1 - cos(grad y, normal) on the surface, | |grad y| - 1 | everywhere, each a mean over all points
+    times the reference's constant. On the GPU, a float32 one-channel output with 2 or 3 input
+    dimensions runs on siren_mri_amd::sdf_loss (siren_sdf.hip: one forward and one backward launch
+    behind diff_operators.gradient); everything else on the expression below."""
+    gt_sdf = gt["sdf"]
+    gt_normals = gt["normals"]
+    coords = model_output["model_in"]
+    pred_sdf = model_output["model_out"]
+
+    gradient = diff_operators.gradient(pred_sdf, coords)
+
+    if _sdf_native_applies(pred_sdf, gradient, gt_sdf, gt_normals):
+        terms = torch.ops.siren_mri_amd.sdf_loss(pred_sdf, gradient, gt_sdf, gt_normals)
+        # terms[0..3] through one unbind: its backward stacks the four upstream scalars in one launch
+        return dict(zip(_SDF_KEYS, terms.unbind(0)))
+    return _sdf_expression(pred_sdf, gradient, gt_sdf, gt_normals)
+
+
+def _sdf_expression(pred_sdf, gradient, gt_sdf, gt_normals):
+    """The reference's expression (loss_functions.py:474-484) in PyTorch ops, on any device and dtype."""
+    on = gt_sdf != -1
+    sdf_constraint = torch.where(on, pred_sdf, torch.zeros_like(pred_sdf))
+    inter_constraint = torch.where(on, torch.zeros_like(pred_sdf), torch.exp(-1e2 * torch.abs(pred_sdf)))
+    cos = torch.nn.functional.cosine_similarity(gradient, gt_normals, dim=-1)[..., None]
+    normal_constraint = torch.where(on, 1 - cos, torch.zeros_like(gradient[..., :1]))
+    grad_constraint = torch.abs(gradient.norm(dim=-1) - 1)
+    return {"sdf": torch.abs(sdf_constraint).mean() * 3e3,
+            "inter": inter_constraint.mean() * 1e2,
+            "normal_constraint": normal_constraint.mean() * 1e2,
+            "grad_constraint": grad_constraint.mean() * 5e1}

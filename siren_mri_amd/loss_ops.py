@@ -8,6 +8,7 @@ the reference-shaped losses and decides when these apply.
   kspace_loss(pred, k0?, mask?, tgt, kind, noise) -> loss, kspace_loss_bwd             (siren_kloss.hip)
   kspace_fft2(x, inverse), kspace_ift_loss(pred, k0?, mask?, tgt, img_mask?, noise, img_weight,
       l1_weight, kspace_weight) -> loss, kspace_ift_loss_bwd                           (siren_kfft.hip)
+  sdf_loss(pred, grad, sdf, normals) -> terms [4], sdf_loss_bwd -> (dpred, dgrad)      (siren_sdf.hip)
 
 pred, tgt are [B, N, C]; k0, mask the [B, C, H, W] planes of a data consistency folded into the loss.
 kspace_sse keeps its residual d for the backward; kspace_loss and kspace_ift_loss recompute dL/dy
@@ -383,3 +384,84 @@ torch.library.register_fake(
     "siren_mri_amd::kspace_ift_loss_bwd",
     lambda pred, k0, mask, tgt, img_mask, g, noise, img_weight, l1_weight, kspace_weight: torch.empty_like(pred),
     lib=_LIB)
+
+
+# ------------------------------------------------------------------ sdf_loss: the signed-distance fitting loss
+# pred, sdf [B, N, 1]; grad, normals [B, N, D], D = 2 or 3. The four terms of loss_functions.sdf as one [4]
+# tensor (sdf, inter, normal_constraint, grad_constraint); the backward recomputes from the same inputs.
+_LIB.define("sdf_loss(Tensor pred, Tensor grad, Tensor sdf, Tensor normals) -> Tensor")
+_LIB.define("sdf_loss_bwd(Tensor pred, Tensor grad, Tensor sdf, Tensor normals, Tensor g) -> (Tensor, Tensor)")
+
+SDF_TERMS = 4
+
+
+def _sdf_operands(pred, grad, sdf, normals):
+    """Contiguous fp32 operands of the SDF loss ops, shapes checked (the kernels index by grad's shape)."""
+    if grad.dim() != 3 or grad.shape[-1] not in (2, 3) or normals.shape != grad.shape:
+        raise RuntimeError(f"siren_mri_amd.sdf_loss: grad {tuple(grad.shape)} must be [B, N, D] with D 2 or 3 and "
+                           f"normals {tuple(normals.shape)} of the same shape")
+    b, n, d = grad.shape
+    for name, t in (("pred", pred), ("sdf", sdf)):
+        if tuple(t.shape) != (b, n, 1):
+            raise RuntimeError(f"siren_mri_amd.sdf_loss: {name} {tuple(t.shape)} must be [{b}, {n}, 1] (one output "
+                               f"channel; the gradient is {tuple(grad.shape)})")
+    for name, t in (("pred", pred), ("grad", grad), ("sdf", sdf), ("normals", normals)):
+        if t.dtype != torch.float32 or t.device != pred.device:
+            raise RuntimeError(f"siren_mri_amd.sdf_loss: {name} must be float32 on {pred.device}")
+    return b * n, d, pred.contiguous(), grad.contiguous(), sdf.contiguous(), normals.contiguous()
+
+
+def _sdf_loss_cuda(pred, grad, sdf, normals):
+    rows, d, pc, gc, sc, nc = _sdf_operands(pred, grad, sdf, normals)
+    out = torch.empty(SDF_TERMS, dtype=torch.float32, device=pred.device)
+    ws = _native.sse_workspace(pred.device)
+    rc = _native.lib().siren_sdf_loss_forward(pc.data_ptr(), gc.data_ptr(), sc.data_ptr(), nc.data_ptr(), rows, d,
+                                              out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _native.stream_handle(pred.device))
+    _native.check(rc, "siren_sdf_loss_forward")
+    return out
+
+
+def _sdf_loss_bwd_cuda(pred, grad, sdf, normals, g):
+    rows, d, pc, gc, sc, nc = _sdf_operands(pred, grad, sdf, normals)
+    if g.numel() != SDF_TERMS or g.device != pred.device:
+        raise RuntimeError(f"siren_mri_amd.sdf_loss_bwd: g must be {SDF_TERMS} elements on the prediction's device")
+    g4 = _g32(g)
+    dpred, dgrad = torch.empty_like(pc), torch.empty_like(gc)
+    rc = _native.lib().siren_sdf_loss_backward(pc.data_ptr(), gc.data_ptr(), sc.data_ptr(), nc.data_ptr(), rows, d,
+                                               g4.data_ptr(), dpred.data_ptr(), dgrad.data_ptr(),
+                                               _native.stream_handle(pred.device))
+    _native.check(rc, "siren_sdf_loss_backward")
+    return dpred, dgrad
+
+
+class _SdfLossAutograd(torch.autograd.Function):
+    """sdf_loss with sdf_loss_bwd as its backward: two differentiable inputs (pred, grad), a [4] upstream;
+    the inputs are saved as they are (no residual is kept)."""
+
+    @staticmethod
+    def forward(ctx, pred, grad, sdf, normals):
+        with torch._C._AutoDispatchBelowAutograd():
+            terms = torch.ops.siren_mri_amd.sdf_loss(pred, grad, sdf, normals)
+        ctx.save_for_backward(pred, grad, sdf, normals)
+        ctx.set_materialize_grads(False)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None, None
+        if torch.is_grad_enabled():
+            raise RuntimeError("siren_mri_amd: double backward through the native SDF loss is not provided; run it on "
+                               "the expression path (siren_mri_amd.loss_functions.set_sdf_loss_native(False))")
+        dpred, dgrad = torch.ops.siren_mri_amd.sdf_loss_bwd(*ctx.saved_tensors, g)
+        return dpred, dgrad, None, None
+
+
+_LIB.impl("sdf_loss", _sdf_loss_cuda, "CUDA")
+_LIB.impl("sdf_loss_bwd", _sdf_loss_bwd_cuda, "CUDA")
+_LIB.impl("sdf_loss", _SdfLossAutograd.apply, "Autograd")
+torch.library.register_fake("siren_mri_amd::sdf_loss", lambda pred, grad, sdf, normals: pred.new_empty((SDF_TERMS,)),
+                            lib=_LIB)
+torch.library.register_fake("siren_mri_amd::sdf_loss_bwd", lambda pred, grad, sdf, normals, g:
+                            (torch.empty_like(pred), torch.empty_like(grad)), lib=_LIB)
