@@ -624,6 +624,41 @@ int siren_sdf_loss_backward(const float* pred, const float* grad, const float* s
                             int dims, const float* g4, float* dpred, float* dgrad, void* stream);
 
 /*
+ * The wave-equation fitting loss (siren_wave.hip; replaces loss_functions.wave_pml, loss_functions.py:358-382)
+ * on the rows of a one-output model of (t, x, y) and of its derivatives. All operands contiguous, float32
+ * except the mask:
+ *   pred [rows]         model output u
+ *   jac  [rows, 3]      diff_operators.jacobian(y, x): u_t = jac[r][0]
+ *   hess [rows, 3, 3]   diff_operators.hessian(y, x), or null: u_tt = h[0][0], lap = h[1][1] + h[2][2]
+ *   src, slow [rows]    the source's boundary values; the squared slowness
+ *   mask [rows] uint8   the Dirichlet mask (torch.bool storage), nonzero = masked
+ * siren_wave_loss_forward   out3 (device) = the reference's three terms, in the order of its dict, with
+ *                    N = rows_per_batch (the rows of one batch element, not rows):
+ *                      [0] dirichlet            (N / 1e1) sum  mask ? |pred - src| : 0
+ *                      [1] neumann              (N / 1e2) sum  mask ? |u_t| : 0
+ *                      [2] diff_constraint_hom  hess ? sum |u_tt - (1 / slow) lap| : 0   (every row)
+ *                    src is read on masked rows only: what an unmasked row holds (NaN included) reaches
+ *                    no result. One launch, deterministic summation order (three sums behind one
+ *                    hand-off ticket, at most 256 workgroups); workspace as siren_sse_forward's
+ *                    (siren_sse_workspace_bytes()). Nothing is kept for the backward. rows == 0: three zeros.
+ * siren_wave_loss_backward  dpred [rows], djac [rows, 3], dhess [rows, 3, 3] = d(sum_k g3[k] out3[k]) /
+ *                    d(pred, jac, hess), recomputed from the same operands in one launch; g3 is a device
+ *                    3-vector. Every element is written (djac[r][1], djac[r][2] and the six off-diagonal
+ *                    entries of dhess[r] with 0), so the buffers need no clearing. sign(0) = 0, as torch's
+ *                    abs backward: pred == src, u_t == 0 and u_tt == lap / slow give exactly 0. dhess is
+ *                    null exactly when hess is. rows == 0: nothing is launched.
+ * SIREN_EINVAL for rows < 0, and with rows > 0 for a null required pointer or rows_per_batch < 1; for a
+ * dhess whose nullness differs from hess's; SIREN_ENOSPACE for a missing or short workspace, as every
+ * loss forward.
+ */
+int siren_wave_loss_forward(const float* pred, const float* jac, const float* hess, const float* src,
+                            const float* slow, const unsigned char* mask, int64_t rows, int64_t rows_per_batch,
+                            float* out3, void* workspace, int64_t ws_bytes, void* stream);
+int siren_wave_loss_backward(const float* pred, const float* jac, const float* hess, const float* src,
+                             const float* slow, const unsigned char* mask, int64_t rows, int64_t rows_per_batch,
+                             const float* g3, float* dpred, float* djac, float* dhess, void* stream);
+
+/*
  * Gaussian Fourier features (replaces GaussianFourierFeatureTransform.forward, features.py:31-41):
  * out [rows, 2 m] = cat(sin(2 pi x B), cos(2 pi x B)) for x [rows, cin], B [cin, m] (device float32),
  * one launch. Feeds the SIREN's wide first layer (5..16 inputs on the register-resident forward).

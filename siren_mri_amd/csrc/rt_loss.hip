@@ -1,5 +1,5 @@
 // rt_loss.hip — image and k-space losses, data consistency, Fourier features and the sin/cos probe
-// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_sdf.hip, siren_kfft.hip). Included
+// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_sdf.hip, siren_wave.hip, siren_kfft.hip). Included
 // by siren_runtime.hip.
 namespace {
 
@@ -81,6 +81,39 @@ SdfArgs sdf_args(const float* pred, const float* grad, const float* sdf, const f
   a.rows = rows;
   const double c[SDF_TERMS] = {3e3, 1e2, 1e2, 5e1};
   for (int k = 0; k < SDF_TERMS; ++k) a.w[k] = rows > 0 ? (float)(c[k] / (double)rows) : 0.f;
+  return a;
+}
+
+// the forms of the wave-equation loss kernels, by whether the Hessian is given
+const Kernel<WaveArgs> kWaveFwd[2] = {SIREN_K(wave_fwd_kernel<false>), SIREN_K(wave_fwd_kernel<true>)};
+const Kernel<WaveArgs> kWaveBwd[2] = {SIREN_K(wave_bwd_kernel<false>), SIREN_K(wave_bwd_kernel<true>)};
+
+// the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
+int wave_check(const char* what, const float* pred, const float* jac, const float* src, const float* slow,
+               const unsigned char* mask, int64_t rows, int64_t rows_per_batch) {
+  if (rows < 0) return fail(SIREN_EINVAL, "%s: bad size (rows=%lld)", what, (long long)rows);
+  if (rows > 0 && rows_per_batch < 1)
+    return fail(SIREN_EINVAL, "%s: bad size (rows_per_batch=%lld)", what, (long long)rows_per_batch);
+  if (rows > 0 && (!pred || !jac || !src || !slow || !mask)) return fail(SIREN_EINVAL, "%s: null pointer", what);
+  return SIREN_OK;
+}
+
+// the reference's constants (loss_functions.py:380-382): sums, the first two times N / 10 and N / 100
+// with N the rows of one batch element
+WaveArgs wave_args(const float* pred, const float* jac, const float* hess, const float* src, const float* slow,
+                   const unsigned char* mask, int64_t rows, int64_t rows_per_batch) {
+  WaveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pred = pred;
+  a.jac = jac;
+  a.hess = hess;
+  a.src = src;
+  a.slow = slow;
+  a.mask = mask;
+  a.rows = rows;
+  a.w[0] = (float)((double)rows_per_batch / 1e1);
+  a.w[1] = (float)((double)rows_per_batch / 1e2);
+  a.w[2] = 1.f;
   return a;
 }
 
@@ -281,6 +314,36 @@ int siren_sdf_loss_backward(const float* pred, const float* grad, const float* s
   a.dgrad = dgrad;
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(rows, SDF_THREADS)));
   return launch_kernel(kSdfBwd[dims - 2], dim3(blocks), SDF_THREADS, 0, "sdf_loss_backward", (hipStream_t)stream, a);
+}
+
+int siren_wave_loss_forward(const float* pred, const float* jac, const float* hess, const float* src,
+                            const float* slow, const unsigned char* mask, int64_t rows, int64_t rows_per_batch,
+                            float* out3, void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = wave_check("wave_loss_forward", pred, jac, src, slow, mask, rows, rows_per_batch)) return rc;
+  if (!out3) return fail(SIREN_EINVAL, "wave_loss_forward: null pointer");
+  WaveArgs a = wave_args(pred, jac, hess, src, slow, mask, rows, rows_per_batch);
+  if (int rc = loss_slots("wave_loss_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
+  a.out = out3;
+  // one row per thread per iteration; three slots per workgroup, at most WAVE_MAX_BLOCKS = 256 of them
+  // (rows == 0: one workgroup writes the three zeros)
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(WAVE_MAX_BLOCKS, cdiv(rows, WAVE_THREADS)));
+  return launch_kernel(kWaveFwd[hess ? 1 : 0], dim3(blocks), WAVE_THREADS, 0, "wave_loss_forward", (hipStream_t)stream, a);
+}
+
+int siren_wave_loss_backward(const float* pred, const float* jac, const float* hess, const float* src,
+                             const float* slow, const unsigned char* mask, int64_t rows, int64_t rows_per_batch,
+                             const float* g3, float* dpred, float* djac, float* dhess, void* stream) {
+  if (int rc = wave_check("wave_loss_backward", pred, jac, src, slow, mask, rows, rows_per_batch)) return rc;
+  if ((!hess) != (!dhess)) return fail(SIREN_EINVAL, "wave_loss_backward: hess and dhess go together");
+  if (rows > 0 && (!g3 || !dpred || !djac)) return fail(SIREN_EINVAL, "wave_loss_backward: null pointer");
+  if (rows == 0) return SIREN_OK;
+  WaveArgs a = wave_args(pred, jac, hess, src, slow, mask, rows, rows_per_batch);
+  a.g = g3;
+  a.dpred = dpred;
+  a.djac = djac;
+  a.dhess = dhess;
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(rows, WAVE_THREADS)));
+  return launch_kernel(kWaveBwd[hess ? 1 : 0], dim3(blocks), WAVE_THREADS, 0, "wave_loss_backward", (hipStream_t)stream, a);
 }
 
 int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream) {

@@ -21,6 +21,7 @@
 #include "siren_kspace.hip"
 #include "siren_kloss.hip"
 #include "siren_sdf.hip"
+#include "siren_wave.hip"
 #include "siren_kfft.hip"
 #include "siren_encoder.hip"
 #include "siren_conv.hip"

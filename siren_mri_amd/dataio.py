@@ -11,6 +11,8 @@ Restated from the reference:
   FastMRIBrainKspace layout  dataio.py:585-664 (fftshift(fft2(slice)) stacked [H, W, 2])
   PointCloud                 dataio.py:401-453 (oriented point cloud -> on- / off-surface SDF batches;
                                                 write_synthetic_point_cloud writes an analytic one)
+  gaussian, WaveSource       dataio.py:115-121, 305-398 (wave-equation batches: (t, x, y) rows, source
+                                                pulse, Dirichlet mask, squared slowness)
 
 Deviation (bug 0.7): fastMRI .h5 volumes are not available, so
 SyntheticMRIKspace produces k-space of seeded phantoms with the same [H, W, 2] float32 layout:
@@ -369,3 +371,102 @@ def write_synthetic_point_cloud(path, shape="torus", n=20000, seed=0):
     cloud = np.concatenate((pts, nrm), axis=1)
     np.savetxt(path, cloud, fmt="%.12f")
     return cloud
+
+
+def gaussian(x, mu=(0, 0), sigma=1e-4, d=2):
+    """The isotropic d-dimensional Gaussian density of variance sigma at the rows of the CPU tensor x
+    [n, d] around mu, evaluated in numpy as the reference does (dataio.py:115-121) and returned as a
+    float32 tensor [n]."""
+    pts = x.numpy()
+    centre = mu.numpy() if isinstance(mu, torch.Tensor) else mu
+    exponent = -0.5 * ((pts - centre) ** 2).sum(1)
+    peak = 1 / np.sqrt(sigma ** d * (2 * np.pi) ** d)
+    return torch.from_numpy(peak * np.exp(exponent / sigma)).float()
+
+
+class WaveSource(Dataset):
+    """Training batches of the wave-equation experiment (dataio.py:305-398): one item is sidelength^2 rows
+    (t, x, y), uniform in space, whose last N_src_samples rows are drawn in a disc around the source, with
+    the ground truth of loss_functions.wave_pml: the Gaussian source pulse as boundary values, the
+    Dirichlet mask of the rows at the start time, and the squared slowness.
+
+    pretrain: every row within 1e-3 of the start time and in the mask; after 2000 items the data set
+    switches itself to training and restarts its counter. Training: t uniform in [0, 0.4 counter / 1e5),
+    so the time window grows with the items drawn, the last 2 N_src_samples rows at the start time.
+    The constructor seeds torch's global generator with 0 and an item draws r, phi, the coordinates and
+    the times from it in that order, which makes the coordinates those of the reference.
+
+    velocity: 'uniform' (slowness 1), or a region of velocity 2 (slowness 1/4): 'square' |x|, |y| < 0.3,
+    'circle' radius 0.1, tested on the two spatial columns (deviation 14: the reference's
+    two branches raise)."""
+
+    def __init__(self, sidelength, velocity="uniform", source_coords=(0., 0., 0.), pretrain=False):
+        super().__init__()
+        torch.manual_seed(0)
+        self.pretrain = pretrain
+        self.sidelength = sidelength
+        self.mgrid = get_mgrid(self.sidelength).detach()
+        self.velocity = velocity
+        self.N_src_samples = 1000
+        self.sigma = 5e-4
+        self.source_coords = torch.tensor(list(source_coords)).view(-1, 3)
+        self.counter = 0
+        self.full_count = 100e3
+
+    def __len__(self):
+        return 1
+
+    def get_squared_slowness(self, coords):
+        """[n] squared slowness at rows whose last two columns are (x, y)."""
+        x, y = coords[..., -2], coords[..., -1]
+        if self.velocity == "square":
+            inside = (torch.abs(x) < 0.3) & (torch.abs(y) < 0.3)
+        elif self.velocity == "circle":
+            inside = torch.sqrt(x ** 2 + y ** 2) < 0.1
+        else:
+            return torch.ones_like(x)
+        perturbation = 2.
+        return torch.where(inside, torch.full_like(x, 1. / perturbation ** 2), torch.ones_like(x))
+
+    def __getitem__(self, idx):
+        start_time = self.source_coords[0, 0]
+        rows, n_src = self.sidelength ** 2, self.N_src_samples
+
+        # the source's disc, uniform by area: the first two draws
+        r = 5e2 * self.sigma * torch.rand(n_src, 1).sqrt()
+        phi = 2 * np.pi * torch.rand(n_src, 1)
+        disc = torch.cat((r * torch.cos(phi) + self.source_coords[0, 1],
+                          r * torch.sin(phi) + self.source_coords[0, 2]), dim=1)
+
+        space = torch.zeros(rows, 2).uniform_(-1, 1)
+        if self.pretrain:
+            time = torch.zeros(rows, 1).uniform_(start_time - 0.001, start_time + 0.001)
+        else:
+            time = torch.zeros(rows, 1).uniform_(0, 0.4 * (self.counter / self.full_count))
+        coords = torch.cat((time, space), dim=1)
+        coords[-n_src:, 1:] = disc
+        if not self.pretrain:
+            coords[-2 * n_src:, 0] = start_time
+
+        normalize = 50 * gaussian(torch.zeros(1, 2), mu=torch.zeros(1, 2), sigma=self.sigma, d=2)
+        boundary_values = gaussian(coords[:, 1:], mu=self.source_coords[:, 1:], sigma=self.sigma, d=2)[:, None]
+        boundary_values /= normalize
+
+        if self.pretrain:
+            dirichlet_mask = torch.ones(rows, 1) > 0
+        else:
+            dirichlet_mask = coords[:, 0, None] == start_time
+            boundary_values = torch.where(dirichlet_mask, boundary_values, torch.Tensor([0]))
+        boundary_values[boundary_values < 1e-5] = 0.
+
+        squared_slowness = self.get_squared_slowness(coords)[:, None]
+        squared_slowness_grid = self.get_squared_slowness(self.mgrid)[:, None]
+
+        self.counter += 1
+        if self.pretrain and self.counter == 2000:
+            self.pretrain = False
+            self.counter = 0
+
+        return {"coords": coords}, {"source_boundary_values": boundary_values, "dirichlet_mask": dirichlet_mask,
+                                    "squared_slowness": squared_slowness,
+                                    "squared_slowness_grid": squared_slowness_grid}

@@ -15,6 +15,8 @@
   laplace_mse              loss_functions.py:350-355
   sdf                      loss_functions.py:460-484 (signed-distance fitting: four terms on the
                            output and its analytic gradient; siren_mri_amd::sdf_loss, siren_sdf.hip)
+  wave_pml                 loss_functions.py:358-382 (wave-equation fitting: three terms on the output,
+                           its analytic Jacobian and Hessian; siren_mri_amd::wave_loss, siren_wave.hip)
 
 image_mse runs on the native k-space op (siren_kspace.hip), with the data consistency of a native
 DataConsistencyInKspace output folded in. The six k-space losses of the
@@ -492,3 +494,80 @@ def _sdf_expression(pred_sdf, gradient, gt_sdf, gt_normals):
             "inter": inter_constraint.mean() * 1e2,
             "normal_constraint": normal_constraint.mean() * 1e2,
             "grad_constraint": grad_constraint.mean() * 5e1}
+
+
+_WAVE_NATIVE = True
+_WAVE_KEYS = ("dirichlet", "neumann", "diff_constraint_hom")
+
+
+def set_wave_loss_native(enabled: bool) -> None:
+    """Run wave_pml on the native op where it applies (default on); off: the reference's expression in
+    PyTorch everywhere (A/B tests)."""
+    global _WAVE_NATIVE
+    _WAVE_NATIVE = bool(enabled)
+
+
+def _wave_native_applies(pred, du, hess, src, slowness, mask):
+    """Whether wave_pml of these operands runs on siren_mri_amd::wave_loss: float32 [B, N, 1] with its
+    [B, N, 1, 3] Jacobian (and [B, N, 1, 3, 3] Hessian, or None) on one GPU, a bool mask, ground truth
+    that needs no gradient."""
+    if not (_WAVE_NATIVE and pred.is_cuda and pred.dim() == 3 and pred.shape[-1] == 1
+            and tuple(du.shape) == (*pred.shape, 3) and (hess is None or tuple(hess.shape) == (*pred.shape, 3, 3))):
+        return False
+    if not (src.shape == pred.shape and slowness.shape == pred.shape and mask.shape == pred.shape):
+        return False
+    floats = [t for t in (pred, du, hess, src, slowness) if t is not None]
+    return all(t.dtype == torch.float32 and t.device == pred.device for t in floats) \
+        and mask.dtype == torch.bool and mask.device == pred.device \
+        and not (src.requires_grad or slowness.requires_grad)
+
+
+def wave_pml(model_output, gt):
+    """loss_functions.py:358-382: the three terms of fitting the wave equation u_tt = lap u / slowness on
+    a batch of (t, x, y) rows: |u - source| and |u_t| on the rows of the Dirichlet mask (the initial
+    condition), times N / 10 and N / 100 with N the rows of a batch element, and |u_tt - lap u / slowness|
+    on every row. While the mask is all true (pretraining; one host read per call, as in the reference)
+    no second derivative is taken and the third term is 0. For a SIREN output the Hessian is
+    diff_operators.hessian's one native pass, differentiable to the parameters; otherwise the
+    reference's jacobian of the Jacobian's first row, by autograd. On the GPU, a float32 one-channel
+    output of 3 inputs runs on siren_mri_amd::wave_loss (siren_wave.hip: one forward and one backward
+    launch); everything else on the expression below."""
+    src = gt["source_boundary_values"]
+    x = model_output["model_in"]
+    y = model_output["model_out"]
+    slowness = gt["squared_slowness"]
+    mask = gt["dirichlet_mask"]
+
+    du, _ = diff_operators.jacobian(y, x)
+    if torch.all(mask):
+        hess = None
+    elif diff_operators.siren_source(y, x) is not None:
+        hess, _ = diff_operators.hessian(y, x)
+    else:
+        hess, _ = diff_operators.jacobian(du[..., 0, :], x)
+        hess = hess.unsqueeze(2)  # [B, N, 3, 3] of output channel 0, in hessian's layout
+
+    if _wave_native_applies(y, du, hess, src, slowness, mask):
+        terms = torch.ops.siren_mri_amd.wave_loss(y, du, hess, src, slowness, mask)
+        # terms[0..2] through one unbind: its backward stacks the three upstream scalars in one launch
+        return dict(zip(_WAVE_KEYS, terms.unbind(0)))
+    return _wave_expression(y, du, hess, src, slowness, mask, x.shape[1])
+
+
+def _wave_expression(y, du, hess, src, slowness, mask, batch_size):
+    """The reference's expression (loss_functions.py:366-382) in PyTorch ops, on any device and dtype:
+    y [B, N, C], du [B, N, C, D], hess [B, N, C, D, D] or None, D >= 2 (time first, the Laplacian over
+    the other dimensions)."""
+    dudt = du[..., 0]
+    if hess is None:
+        diff_constraint_hom = torch.zeros(1, dtype=y.dtype, device=y.device)
+    else:
+        lap = hess[..., 1:, 1:].diagonal(dim1=-2, dim2=-1).sum(-1)
+        dudt2 = hess[..., 0, 0]
+        diff_constraint_hom = dudt2 - 1 / slowness * lap
+    m = mask.expand_as(y)
+    dirichlet = y[m] - src.expand_as(y)[m]
+    neumann = dudt[m]
+    return {"dirichlet": torch.abs(dirichlet).sum() * batch_size / 1e1,
+            "neumann": torch.abs(neumann).sum() * batch_size / 1e2,
+            "diff_constraint_hom": torch.abs(diff_constraint_hom).sum()}

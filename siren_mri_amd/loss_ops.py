@@ -9,6 +9,8 @@ the reference-shaped losses and decides when these apply.
   kspace_fft2(x, inverse), kspace_ift_loss(pred, k0?, mask?, tgt, img_mask?, noise, img_weight,
       l1_weight, kspace_weight) -> loss, kspace_ift_loss_bwd                           (siren_kfft.hip)
   sdf_loss(pred, grad, sdf, normals) -> terms [4], sdf_loss_bwd -> (dpred, dgrad)      (siren_sdf.hip)
+  wave_loss(pred, jac, hess?, src, slowness, mask) -> terms [3], wave_loss_bwd -> (dpred, djac, dhess)
+                                                                                       (siren_wave.hip)
 
 pred, tgt are [B, N, C]; k0, mask the [B, C, H, W] planes of a data consistency folded into the loss.
 kspace_sse keeps its residual d for the backward; kspace_loss and kspace_ift_loss recompute dL/dy
@@ -465,3 +467,98 @@ torch.library.register_fake("siren_mri_amd::sdf_loss", lambda pred, grad, sdf, n
                             lib=_LIB)
 torch.library.register_fake("siren_mri_amd::sdf_loss_bwd", lambda pred, grad, sdf, normals, g:
                             (torch.empty_like(pred), torch.empty_like(grad)), lib=_LIB)
+
+
+# ------------------------------------------------------------------ wave_loss: the wave-equation fitting loss
+# pred, src, slowness, mask [B, N, 1] (mask torch.bool); jac [B, N, 1, 3]; hess [B, N, 1, 3, 3] or None (the
+# pretraining batches, whose mask is all true). The three terms of loss_functions.wave_pml as one [3]
+# tensor (dirichlet, neumann, diff_constraint_hom); the backward recomputes from the same inputs.
+_LIB.define("wave_loss(Tensor pred, Tensor jac, Tensor? hess, Tensor src, Tensor slowness, Tensor mask) -> Tensor")
+_LIB.define("wave_loss_bwd(Tensor pred, Tensor jac, Tensor? hess, Tensor src, Tensor slowness, Tensor mask, Tensor g) "
+            "-> (Tensor, Tensor, Tensor)")
+
+WAVE_TERMS = 3
+
+
+def _wave_operands(pred, jac, hess, src, slowness, mask):
+    """Contiguous operands of the wave loss ops, shapes checked (the kernels index by pred's shape); the
+    bool mask as a uint8 view of the same storage."""
+    if pred.dim() != 3 or pred.shape[-1] != 1:
+        raise RuntimeError(f"siren_mri_amd.wave_loss: pred {tuple(pred.shape)} must be [B, N, 1] (one output channel)")
+    b, n, _ = pred.shape
+    if tuple(jac.shape) != (b, n, 1, 3):
+        raise RuntimeError(f"siren_mri_amd.wave_loss: jac {tuple(jac.shape)} must be [{b}, {n}, 1, 3] (inputs t, x, y)")
+    if hess is not None and tuple(hess.shape) != (b, n, 1, 3, 3):
+        raise RuntimeError(f"siren_mri_amd.wave_loss: hess {tuple(hess.shape)} must be [{b}, {n}, 1, 3, 3]")
+    for name, t in (("src", src), ("slowness", slowness), ("mask", mask)):
+        if tuple(t.shape) != (b, n, 1):
+            raise RuntimeError(f"siren_mri_amd.wave_loss: {name} {tuple(t.shape)} must be [{b}, {n}, 1]")
+    for name, t in (("pred", pred), ("jac", jac), ("hess", hess), ("src", src), ("slowness", slowness)):
+        if t is not None and (t.dtype != torch.float32 or t.device != pred.device):
+            raise RuntimeError(f"siren_mri_amd.wave_loss: {name} must be float32 on {pred.device}")
+    if mask.dtype != torch.bool or mask.device != pred.device:
+        raise RuntimeError(f"siren_mri_amd.wave_loss: mask must be bool on {pred.device}")
+    return (b * n, n, pred.contiguous(), jac.contiguous(), _contig(hess), src.contiguous(), slowness.contiguous(),
+            mask.contiguous().view(torch.uint8))
+
+
+def _wave_loss_cuda(pred, jac, hess, src, slowness, mask):
+    rows, n, pc, jc, hc, sc, lc, mc = _wave_operands(pred, jac, hess, src, slowness, mask)
+    out = torch.empty(WAVE_TERMS, dtype=torch.float32, device=pred.device)
+    ws = _native.sse_workspace(pred.device)
+    rc = _native.lib().siren_wave_loss_forward(pc.data_ptr(), jc.data_ptr(), _ptr(hc), sc.data_ptr(), lc.data_ptr(),
+                                               mc.data_ptr(), rows, n, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               _native.stream_handle(pred.device))
+    _native.check(rc, "siren_wave_loss_forward")
+    return out
+
+
+def _wave_loss_bwd_cuda(pred, jac, hess, src, slowness, mask, g):
+    rows, n, pc, jc, hc, sc, lc, mc = _wave_operands(pred, jac, hess, src, slowness, mask)
+    if g.numel() != WAVE_TERMS or g.device != pred.device:
+        raise RuntimeError(f"siren_mri_amd.wave_loss_bwd: g must be {WAVE_TERMS} elements on the prediction's device")
+    g3 = _g32(g)
+    dpred, djac = torch.empty_like(pc), torch.empty_like(jc)
+    dhess = torch.empty_like(hc) if hc is not None else pred.new_empty((0,))
+    rc = _native.lib().siren_wave_loss_backward(pc.data_ptr(), jc.data_ptr(), _ptr(hc), sc.data_ptr(), lc.data_ptr(),
+                                                mc.data_ptr(), rows, n, g3.data_ptr(), dpred.data_ptr(),
+                                                djac.data_ptr(), dhess.data_ptr() if hc is not None else None,
+                                                _native.stream_handle(pred.device))
+    _native.check(rc, "siren_wave_loss_backward")
+    return dpred, djac, dhess
+
+
+class _WaveLossAutograd(torch.autograd.Function):
+    """wave_loss with wave_loss_bwd as its backward: three differentiable inputs (pred, jac, hess), a [3]
+    upstream; the inputs are saved as they are (no residual is kept)."""
+
+    @staticmethod
+    def forward(ctx, pred, jac, hess, src, slowness, mask):
+        with torch._C._AutoDispatchBelowAutograd():
+            terms = torch.ops.siren_mri_amd.wave_loss(pred, jac, hess, src, slowness, mask)
+        ctx.save_for_backward(pred, jac, hess, src, slowness, mask)
+        ctx.set_materialize_grads(False)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 6
+        if torch.is_grad_enabled():
+            raise RuntimeError("siren_mri_amd: double backward through the native wave loss is not provided; run it on "
+                               "the expression path (siren_mri_amd.loss_functions.set_wave_loss_native(False))")
+        dpred, djac, dhess = torch.ops.siren_mri_amd.wave_loss_bwd(*ctx.saved_tensors, g)
+        return dpred, djac, (dhess if ctx.saved_tensors[2] is not None else None), None, None, None
+
+
+def _wave_loss_bwd_fake(pred, jac, hess, src, slowness, mask, g):
+    return (torch.empty_like(pred), torch.empty_like(jac),
+            torch.empty_like(hess) if hess is not None else pred.new_empty((0,)))
+
+
+_LIB.impl("wave_loss", _wave_loss_cuda, "CUDA")
+_LIB.impl("wave_loss_bwd", _wave_loss_bwd_cuda, "CUDA")
+_LIB.impl("wave_loss", _WaveLossAutograd.apply, "Autograd")
+torch.library.register_fake("siren_mri_amd::wave_loss",
+                            lambda pred, jac, hess, src, slowness, mask: pred.new_empty((WAVE_TERMS,)), lib=_LIB)
+torch.library.register_fake("siren_mri_amd::wave_loss_bwd", _wave_loss_bwd_fake, lib=_LIB)
