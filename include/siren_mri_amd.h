@@ -659,6 +659,48 @@ int siren_wave_loss_backward(const float* pred, const float* jac, const float* h
                              const float* g3, float* dpred, float* djac, float* dhess, void* stream);
 
 /*
+ * The Helmholtz fitting loss (siren_helmholtz.hip; replaces the forward problem of loss_functions.helmholtz_pml,
+ * loss_functions.py:385-457) on the rows of a two-output model of (x0, x1), the complex field
+ * u = pred[0] + i pred[1], and of its derivatives. All operands contiguous float32:
+ *   x    [rows, 2]        coordinates
+ *   pred [rows, 2]        u
+ *   jac  [rows, 2, 2]     jac[c][d] = d pred_c / d x_d:  u_d = jac[0][d] + i jac[1][d]
+ *   hess [rows, 2, 2, 2]  hess[c][j][k], only j == k is read:  u_dd = hess[0][d][d] + i hess[1][d][d]
+ *   src  [rows, 2]        source_boundary_values
+ *   slow [rows, 2]        the squared slowness m = slow[0] + i slow[1]
+ *   k    [1]              the wavenumber (device memory: no host read)
+ * With a0 = 5, L = 0.5 and, per row,
+ *   dw = max(-(x0 + 0.5), 0)  de = max(x0 - 0.5, 0)  ds = max(-(x1 + 0.5), 0)  dn = max(x1 - 0.5, 0)
+ *   px = a0 (dw^2 + de^2) / L^2   py = a0 (dn^2 + ds^2) / L^2   px' = 2 a0 (de - dw) / L^2   py' = 2 a0 (dn - ds) / L^2
+ *   ex = 1 - i px   ey = 1 - i py   A = ey / ex   B = ex / ey   C = ex ey   A_x0 = i px' ey / ex^2   B_x1 = i py' ex / ey^2
+ * the residual is e = A_x0 u_0 + A u_00 + B_x1 u_1 + B u_11 + k^2 C m u (the reference's jacobian of A u_0 and
+ * B u_1 by the product rule).
+ * siren_helmholtz_loss_forward   out3 (device) = the reference's three terms, in the order of its dict, with
+ *                    N = rows_per_batch (the rows of one batch element, not rows) and c over the real and the
+ *                    imaginary channel, on or off decided per element:
+ *                      [0] diff_constraint_on   (N / 1e3) sum  src_c != 0 ? |e_c - src_c| : 0
+ *                      [1] diff_constraint_off  sum  src_c == 0 ? |e_c| : 0
+ *                      [2] data_term            0
+ *                    One launch, deterministic summation order (two sums behind one hand-off ticket, at most
+ *                    256 workgroups); workspace as siren_sse_forward's (siren_sse_workspace_bytes()). Nothing
+ *                    is kept for the backward. rows == 0: three zeros, no kernel is launched.
+ * siren_helmholtz_loss_backward  dpred [rows, 2], djac [rows, 2, 2], dhess [rows, 2, 2, 2] = d(sum_k g3[k] out3[k])
+ *                    / d(pred, jac, hess), recomputed from the same operands in one launch; g3 is a device
+ *                    3-vector whose last element is not read. Every element is written (the four off-diagonal
+ *                    entries of dhess[r] with 0), so the buffers need no clearing. sign(0) = 0, as torch's abs
+ *                    backward. No gradient reaches x through the coefficients. rows == 0: nothing is launched.
+ * SIREN_EINVAL for rows < 0, and with rows > 0 for a null pointer or rows_per_batch < 1; SIREN_ENOSPACE for
+ * a missing or short workspace, as every loss forward.
+ */
+int siren_helmholtz_loss_forward(const float* x, const float* pred, const float* jac, const float* hess,
+                                 const float* src, const float* slow, const float* k, int64_t rows,
+                                 int64_t rows_per_batch, float* out3, void* workspace, int64_t ws_bytes, void* stream);
+int siren_helmholtz_loss_backward(const float* x, const float* pred, const float* jac, const float* hess,
+                                  const float* src, const float* slow, const float* k, int64_t rows,
+                                  int64_t rows_per_batch, const float* g3, float* dpred, float* djac, float* dhess,
+                                  void* stream);
+
+/*
  * Gaussian Fourier features (replaces GaussianFourierFeatureTransform.forward, features.py:31-41):
  * out [rows, 2 m] = cat(sin(2 pi x B), cos(2 pi x B)) for x [rows, cin], B [cin, m] (device float32),
  * one launch. Feeds the SIREN's wide first layer (5..16 inputs on the register-resident forward).

@@ -252,6 +252,8 @@ def _signatures():
         "siren_sdf_loss_backward": (ci, [vp, vp, vp, vp, i64, ci, vp, vp, vp, vp]),
         "siren_wave_loss_forward": (ci, [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp]),
         "siren_wave_loss_backward": (ci, [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
+        "siren_helmholtz_loss_forward": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp]),
+        "siren_helmholtz_loss_backward": (ci, [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]),
         "siren_fourier_features": (ci, [vp, vp, i64, ci, ci, vp, vp]),
         "siren_sincos_f32": (ci, [vp, vp, vp, i64, ci, vp]),
         "siren_last_error": (cstr, []),

@@ -1,6 +1,6 @@
 // rt_loss.hip — image and k-space losses, data consistency, Fourier features and the sin/cos probe
-// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_sdf.hip, siren_wave.hip, siren_kfft.hip). Included
-// by siren_runtime.hip.
+// (kernels in siren_loss.hip, siren_kspace.hip, siren_kloss.hip, siren_sdf.hip, siren_wave.hip, siren_helmholtz.hip,
+// siren_kfft.hip). Included by siren_runtime.hip.
 namespace {
 
 // The hand-off workspace of a loss forward, checked and sliced; 0 or SIREN_ENOSPACE (message set), as
@@ -114,6 +114,39 @@ WaveArgs wave_args(const float* pred, const float* jac, const float* hess, const
   a.w[0] = (float)((double)rows_per_batch / 1e1);
   a.w[1] = (float)((double)rows_per_batch / 1e2);
   a.w[2] = 1.f;
+  return a;
+}
+
+// the Helmholtz loss kernels
+const Kernel<HelmArgs> kHelmFwd = SIREN_K(helmholtz_fwd_kernel);
+const Kernel<HelmArgs> kHelmBwd = SIREN_K(helmholtz_bwd_kernel);
+
+// the argument checks both entry points share; 0 or SIREN_EINVAL (message set)
+int helm_check(const char* what, const float* x, const float* pred, const float* jac, const float* hess,
+               const float* src, const float* slow, const float* k, int64_t rows, int64_t rows_per_batch) {
+  if (rows < 0) return fail(SIREN_EINVAL, "%s: bad size (rows=%lld)", what, (long long)rows);
+  if (rows > 0 && rows_per_batch < 1)
+    return fail(SIREN_EINVAL, "%s: bad size (rows_per_batch=%lld)", what, (long long)rows_per_batch);
+  if (rows > 0 && (!x || !pred || !jac || !hess || !src || !slow || !k)) return fail(SIREN_EINVAL, "%s: null pointer", what);
+  return SIREN_OK;
+}
+
+// the reference's constants (loss_functions.py:455-456): sums, the first times N / 1e3 with N the rows of
+// one batch element
+HelmArgs helm_args(const float* x, const float* pred, const float* jac, const float* hess, const float* src,
+                   const float* slow, const float* k, int64_t rows, int64_t rows_per_batch) {
+  HelmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x;
+  a.pred = pred;
+  a.jac = jac;
+  a.hess = hess;
+  a.src = src;
+  a.slow = slow;
+  a.k = k;
+  a.rows = rows;
+  a.w[0] = (float)((double)rows_per_batch / 1e3);
+  a.w[1] = 1.f;
   return a;
 }
 
@@ -344,6 +377,40 @@ int siren_wave_loss_backward(const float* pred, const float* jac, const float* h
   a.dhess = dhess;
   const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(4096, cdiv(rows, WAVE_THREADS)));
   return launch_kernel(kWaveBwd[hess ? 1 : 0], dim3(blocks), WAVE_THREADS, 0, "wave_loss_backward", (hipStream_t)stream, a);
+}
+
+int siren_helmholtz_loss_forward(const float* x, const float* pred, const float* jac, const float* hess,
+                                 const float* src, const float* slow, const float* k, int64_t rows,
+                                 int64_t rows_per_batch, float* out3, void* workspace, int64_t ws_bytes, void* stream) {
+  if (int rc = helm_check("helmholtz_loss_forward", x, pred, jac, hess, src, slow, k, rows, rows_per_batch)) return rc;
+  if (!out3) return fail(SIREN_EINVAL, "helmholtz_loss_forward: null pointer");
+  HelmArgs a = helm_args(x, pred, jac, hess, src, slow, k, rows, rows_per_batch);
+  if (int rc = loss_slots("helmholtz_loss_forward", workspace, ws_bytes, &a.partial, &a.counter)) return rc;
+  if (rows == 0) {  // three zeros, no launch
+    if (hipMemsetAsync(out3, 0, 3 * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      return fail(SIREN_ELAUNCH, "helmholtz_loss_forward: %s", hipGetErrorString(hipGetLastError()));
+    return SIREN_OK;
+  }
+  a.out = out3;
+  // one row per thread per iteration; two slots per workgroup, at most HELM_MAX_BLOCKS = 256 of them
+  const unsigned blocks = (unsigned)std::min<int64_t>(HELM_MAX_BLOCKS, cdiv(rows, HELM_THREADS));
+  return launch_kernel(kHelmFwd, dim3(blocks), HELM_THREADS, 0, "helmholtz_loss_forward", (hipStream_t)stream, a);
+}
+
+int siren_helmholtz_loss_backward(const float* x, const float* pred, const float* jac, const float* hess,
+                                  const float* src, const float* slow, const float* k, int64_t rows,
+                                  int64_t rows_per_batch, const float* g3, float* dpred, float* djac, float* dhess,
+                                  void* stream) {
+  if (int rc = helm_check("helmholtz_loss_backward", x, pred, jac, hess, src, slow, k, rows, rows_per_batch)) return rc;
+  if (rows > 0 && (!g3 || !dpred || !djac || !dhess)) return fail(SIREN_EINVAL, "helmholtz_loss_backward: null pointer");
+  if (rows == 0) return SIREN_OK;
+  HelmArgs a = helm_args(x, pred, jac, hess, src, slow, k, rows, rows_per_batch);
+  a.g = g3;
+  a.dpred = dpred;
+  a.djac = djac;
+  a.dhess = dhess;
+  const unsigned blocks = (unsigned)std::min<int64_t>(4096, cdiv(rows, HELM_THREADS));
+  return launch_kernel(kHelmBwd, dim3(blocks), HELM_THREADS, 0, "helmholtz_loss_backward", (hipStream_t)stream, a);
 }
 
 int siren_kspace_fft2(const float* x, float* out, int64_t batch, int side, int inverse, void* stream) {

@@ -22,6 +22,7 @@
 #include "siren_kloss.hip"
 #include "siren_sdf.hip"
 #include "siren_wave.hip"
+#include "siren_helmholtz.hip"
 #include "siren_kfft.hip"
 #include "siren_encoder.hip"
 #include "siren_conv.hip"

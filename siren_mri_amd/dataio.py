@@ -13,6 +13,8 @@ Restated from the reference:
                                                 write_synthetic_point_cloud writes an analytic one)
   gaussian, WaveSource       dataio.py:115-121, 305-398 (wave-equation batches: (t, x, y) rows, source
                                                 pulse, Dirichlet mask, squared slowness)
+  SingleHelmholtzSource      dataio.py:220-302 (Helmholtz batches: (x0, x1) rows, the complex source, squared
+                                                slowness, wavenumber, the closed-form field)
 
 Deviation (bug 0.7): fastMRI .h5 volumes are not available, so
 SyntheticMRIKspace produces k-space of seeded phantoms with the same [H, W, 2] float32 layout:
@@ -470,3 +472,85 @@ class WaveSource(Dataset):
         return {"coords": coords}, {"source_boundary_values": boundary_values, "dirichlet_mask": dirichlet_mask,
                                     "squared_slowness": squared_slowness,
                                     "squared_slowness_grid": squared_slowness_grid}
+
+
+class SingleHelmholtzSource(Dataset):
+    """Training batches of the Helmholtz experiment (dataio.py:220-302): one item is sidelength^2 rows
+    (x0, x1) uniform in [-1, 1]^2, whose last N_src_samples rows are drawn in a disc around the source, with
+    the ground truth of loss_functions.helmholtz_pml: the complex source (1 + i) times a Gaussian as
+    boundary values [n, 2] (values below 1e-5 are 0, which encodes "no source here"), the squared slowness
+    as a complex number [n, 2], and the wavenumber 20. The constructor seeds torch's global generator with
+    0 and an item draws the coordinates, r and phi from it in that order, which makes the items those of
+    the reference.
+
+    velocity: 'uniform' (slowness 1), or a region of velocity 2 (slowness 1/4): 'square' |x0|, |x1| < 0.3,
+    'circle' radius 0.1.
+
+    field [sidelength^2, 2] (gt['gt']) is the closed-form comparison solution of the uniform medium on
+    get_mgrid(sidelength), 0.25 i H0^(2)(k r + 1e-6) s hx hy per source; it never enters the loss. The Hankel
+    function is J0 - i Y0 of torch.special (the reference calls scipy.special.hankel2), evaluated on the
+    reference's float32 argument, rounded to complex64 and accumulated in complex64."""
+
+    def __init__(self, sidelength, velocity="uniform", source_coords=(0., 0.)):
+        super().__init__()
+        torch.manual_seed(0)
+        self.sidelength = sidelength
+        self.mgrid = get_mgrid(self.sidelength).detach()
+        self.velocity = velocity
+        self.wavenumber = 20.
+        self.N_src_samples = 100
+        self.sigma = 1e-4
+        self.source = torch.Tensor([1.0, 1.0]).view(-1, 2)
+        self.source_coords = torch.tensor(list(source_coords)).view(-1, 2)
+
+        x = self.mgrid[:, 0].view(sidelength, sidelength)
+        y = self.mgrid[:, 1].view(sidelength, sidelength)
+        hx = hy = 2 / self.sidelength
+        field = torch.zeros(sidelength, sidelength, dtype=torch.complex64)
+        for i in range(self.source.shape[0]):
+            x0, y0 = self.source_coords[i, 0], self.source_coords[i, 1]
+            s = complex(float(self.source[i, 0]), float(self.source[i, 1]))
+            arg = self.wavenumber * torch.sqrt((x - x0) ** 2 + (y - y0) ** 2) + 1e-6
+            # the float32 argument, the two Bessel functions evaluated in float64 on it (as scipy's float32
+            # loop does internally), rounded to complex64
+            arg = arg.double()
+            hankel = torch.complex(torch.special.bessel_j0(arg), -torch.special.bessel_y0(arg)).to(torch.complex64)
+            field = field + 0.25j * hankel * s * hx * hy
+        self.field = torch.cat((field.real.reshape(-1, 1), field.imag.reshape(-1, 1)), dim=1)
+
+    def __len__(self):
+        return 1
+
+    def get_squared_slowness(self, coords):
+        """[n, 2] squared slowness (real, imaginary = 0) at the rows (x0, x1)."""
+        x, y = coords[..., 0], coords[..., 1]
+        if self.velocity == "square":
+            inside = (torch.abs(x) < 0.3) & (torch.abs(y) < 0.3)
+        elif self.velocity == "circle":
+            inside = torch.sqrt(x ** 2 + y ** 2) < 0.1
+        else:
+            inside = torch.zeros_like(x, dtype=torch.bool)
+        perturbation = 2.
+        real = torch.where(inside, torch.full_like(x, 1. / perturbation ** 2), torch.ones_like(x))
+        return torch.stack((real, torch.zeros_like(real)), dim=-1)
+
+    def __getitem__(self, idx):
+        n_src = self.N_src_samples
+        coords = torch.zeros(self.sidelength ** 2, 2).uniform_(-1., 1.)
+        # the source's disc, uniform by area
+        r = 5e2 * self.sigma * torch.rand(n_src, 1).sqrt()
+        phi = 2 * np.pi * torch.rand(n_src, 1)
+        coords[-n_src:, :] = torch.cat((r * torch.cos(phi) + self.source_coords[0, 0],
+                                        r * torch.sin(phi) + self.source_coords[0, 1]), dim=1)
+
+        # the value 0 encodes "no boundary constraint at this coordinate"
+        boundary_values = self.source * gaussian(coords, mu=self.source_coords, sigma=self.sigma)[:, None]
+        boundary_values[boundary_values < 1e-5] = 0.
+
+        squared_slowness = self.get_squared_slowness(coords)
+        squared_slowness_grid = self.get_squared_slowness(self.mgrid)[:, 0, None]
+
+        return {"coords": coords}, {"source_boundary_values": boundary_values, "gt": self.field,
+                                    "squared_slowness": squared_slowness,
+                                    "squared_slowness_grid": squared_slowness_grid,
+                                    "wavenumber": self.wavenumber}

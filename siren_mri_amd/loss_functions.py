@@ -17,6 +17,9 @@
                            output and its analytic gradient; siren_mri_amd::sdf_loss, siren_sdf.hip)
   wave_pml                 loss_functions.py:358-382 (wave-equation fitting: three terms on the output,
                            its analytic Jacobian and Hessian; siren_mri_amd::wave_loss, siren_wave.hip)
+  helmholtz_pml            loss_functions.py:385-457, the forward problem (Helmholtz fitting with a perfectly
+                           matched layer: two sums on the complex output, its analytic Jacobian and
+                           Hessian; siren_mri_amd::helmholtz_loss, siren_helmholtz.hip)
 
 image_mse runs on the native k-space op (siren_kspace.hip), with the data consistency of a native
 DataConsistencyInKspace output folded in. The six k-space losses of the
@@ -571,3 +574,100 @@ def _wave_expression(y, du, hess, src, slowness, mask, batch_size):
     return {"dirichlet": torch.abs(dirichlet).sum() * batch_size / 1e1,
             "neumann": torch.abs(neumann).sum() * batch_size / 1e2,
             "diff_constraint_hom": torch.abs(diff_constraint_hom).sum()}
+
+
+_HELMHOLTZ_NATIVE = True
+_HELMHOLTZ_KEYS = ("diff_constraint_on", "diff_constraint_off", "data_term")
+
+
+def set_helmholtz_loss_native(enabled: bool) -> None:
+    """Run helmholtz_pml on the native op where it applies (default on); off: the same formulas in PyTorch
+    ops everywhere (A/B tests, double backward)."""
+    global _HELMHOLTZ_NATIVE
+    _HELMHOLTZ_NATIVE = bool(enabled)
+
+
+def _helmholtz_native_applies(x, y, du, hess, src, slowness, wavenumber):
+    """Whether helmholtz_pml of these operands runs on siren_mri_amd::helmholtz_loss: float32 x, y [B, N, 2]
+    with the [B, N, 2, 2] Jacobian and [B, N, 2, 2, 2] Hessian on one GPU, a one-element wavenumber, ground
+    truth that needs no gradient."""
+    if not (_HELMHOLTZ_NATIVE and y.is_cuda and y.dim() == 3 and y.shape[-1] == 2 and x.shape == y.shape
+            and tuple(du.shape) == (*y.shape, 2) and tuple(hess.shape) == (*y.shape, 2, 2)):
+        return False
+    if not (src.shape == y.shape and slowness.shape == y.shape and wavenumber.numel() == 1):
+        return False
+    return all(t.dtype == torch.float32 and t.device == y.device for t in (x, y, du, hess, src, slowness, wavenumber)) \
+        and not (src.requires_grad or slowness.requires_grad or wavenumber.requires_grad)
+
+
+def helmholtz_pml(model_output, gt):
+    """The forward problem of loss_functions.py:385-457: the terms of fitting the Helmholtz equation with a
+    perfectly matched layer, div(S grad u) + k^2 C m u = source for the complex field u = y[..., 0] + i y[..., 1]
+    of (x0, x1): |e - source| on the elements whose source value is nonzero, times N / 1e3 with N the rows of
+    a batch element; |e| on the others; and a data term that the forward problem leaves 0 (on the operands'
+    device; the reference's is a CPU tensor).
+
+    The reference takes jacobian(compl_mul(A, u_0), x) by autograd through the layer's coefficients A(x),
+    B(x); here the product rule is written out, e = A_x0 u_0 + A u_00 + B_x1 u_1 + B u_11 + k^2 C m u, so the
+    loss is linear in y, diff_operators.jacobian(y, x) and the diagonal of diff_operators.hessian(y, x): for
+    a SIREN output two native passes, differentiable to the parameters. The loss is differentiable in y and
+    its derivatives only: no gradient reaches x through the coefficients (training discards it, model_in
+    being a detached leaf). On the GPU, a float32 two-channel output of 2 inputs with a one-element
+    wavenumber runs on siren_mri_amd::helmholtz_loss (siren_helmholtz.hip: one forward and one backward
+    launch); everything else on _helmholtz_expression below. The inverse problem ('pretrain' or
+    'rec_boundary_values' in gt) is out of scope."""
+    if "pretrain" in gt or "rec_boundary_values" in gt:
+        raise NotImplementedError("helmholtz_pml: the inverse problem (full-waveform inversion: 'pretrain' / "
+                                  "'rec_boundary_values' in gt) is out of scope; the forward problem is provided")
+    src = gt["source_boundary_values"]
+    x = model_output["model_in"]
+    y = model_output["model_out"]
+    slowness = gt["squared_slowness"]
+    wavenumber = torch.as_tensor(gt["wavenumber"], device=y.device)
+    wavenumber = wavenumber.to(y.dtype if y.dtype == torch.float64 else torch.float32)
+
+    du, _ = diff_operators.jacobian(y, x)
+    hess, _ = diff_operators.hessian(y, x)
+
+    if _helmholtz_native_applies(x, y, du, hess, src, slowness, wavenumber):
+        terms = torch.ops.siren_mri_amd.helmholtz_loss(x.detach(), y, du, hess, src, slowness, wavenumber)
+        # terms[0..2] through one unbind: its backward stacks the three upstream scalars in one launch
+        return dict(zip(_HELMHOLTZ_KEYS, terms.unbind(0)))
+    return _helmholtz_expression(x, y, du, hess, src, slowness, wavenumber)
+
+
+def _helmholtz_expression(x, y, du, hess, src, slowness, wavenumber):
+    """helmholtz_pml's formulas in PyTorch ops, on any device and dtype: x [B, N, 2]; y, src [B, N, C] with
+    C = 2 P interleaved real / imaginary channels; du [B, N, C, 2]; hess [B, N, C, 2, 2]; slowness [B, N, 2].
+    The coefficients and the slowness are repeated over the P fields, as the reference's .repeat does."""
+    from . import modules
+    a0, lpml = 5.0, 0.5
+    pairs = y.shape[-1] // 2
+    batch_size = x.shape[1]
+    xd = x.detach()
+    zero = torch.zeros_like(xd[..., :1])
+    one = torch.ones_like(zero)
+
+    def layer(t):  # a0 (lo^2 + hi^2) / L^2 and its derivative, [B, N, 1]
+        lo = -torch.clamp(t + (1.0 - lpml), max=0)
+        hi = torch.clamp(t - (1.0 - lpml), min=0)
+        return a0 * (lo ** 2 + hi ** 2) / lpml ** 2, 2 * a0 * (hi - lo) / lpml ** 2
+
+    px, dpx = layer(xd[..., 0:1])
+    py, dpy = layer(xd[..., 1:2])
+    ex, ey = torch.cat((one, -px), dim=-1), torch.cat((one, -py), dim=-1)
+    A, B, C = modules.compl_div(ey, ex), modules.compl_div(ex, ey), modules.compl_mul(ex, ey)
+    Ax = modules.compl_mul(torch.cat((zero, dpx), dim=-1), modules.compl_div(A, ex))  # i px' ey / ex^2
+    Bx = modules.compl_mul(torch.cat((zero, dpy), dim=-1), modules.compl_div(B, ey))
+    A, B, C, Ax, Bx, m = (t.repeat(1, 1, pairs) for t in (A, B, C, Ax, Bx, slowness))
+
+    e = (modules.compl_mul(Ax, du[..., 0]) + modules.compl_mul(A, hess[..., 0, 0])
+         + modules.compl_mul(Bx, du[..., 1]) + modules.compl_mul(B, hess[..., 1, 1])
+         + modules.compl_mul(modules.compl_mul(C, m), wavenumber ** 2 * y))
+    off = torch.zeros_like(e)
+    diff_constraint_on = torch.where(src != 0., e - src, off)
+    diff_constraint_off = torch.where(src == 0., e, off)
+    data_term = torch.zeros(1, dtype=y.dtype, device=y.device)
+    return {"diff_constraint_on": torch.abs(diff_constraint_on).sum() * batch_size / 1e3,
+            "diff_constraint_off": torch.abs(diff_constraint_off).sum(),
+            "data_term": torch.abs(data_term).sum() * batch_size / 1}

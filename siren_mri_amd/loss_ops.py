@@ -11,6 +11,8 @@ the reference-shaped losses and decides when these apply.
   sdf_loss(pred, grad, sdf, normals) -> terms [4], sdf_loss_bwd -> (dpred, dgrad)      (siren_sdf.hip)
   wave_loss(pred, jac, hess?, src, slowness, mask) -> terms [3], wave_loss_bwd -> (dpred, djac, dhess)
                                                                                        (siren_wave.hip)
+  helmholtz_loss(x, pred, jac, hess, src, slowness, wavenumber) -> terms [3], helmholtz_loss_bwd ->
+      (dpred, djac, dhess)                                                        (siren_helmholtz.hip)
 
 pred, tgt are [B, N, C]; k0, mask the [B, C, H, W] planes of a data consistency folded into the loss.
 kspace_sse keeps its residual d for the backward; kspace_loss and kspace_ift_loss recompute dL/dy
@@ -562,3 +564,94 @@ _LIB.impl("wave_loss", _WaveLossAutograd.apply, "Autograd")
 torch.library.register_fake("siren_mri_amd::wave_loss",
                             lambda pred, jac, hess, src, slowness, mask: pred.new_empty((WAVE_TERMS,)), lib=_LIB)
 torch.library.register_fake("siren_mri_amd::wave_loss_bwd", _wave_loss_bwd_fake, lib=_LIB)
+
+
+# ------------------------------------------------------------------ helmholtz_loss: the Helmholtz fitting loss
+# x, pred, src, slowness [B, N, 2] (pred, src and slowness as real / imaginary channels); jac [B, N, 2, 2];
+# hess [B, N, 2, 2, 2]; wavenumber one element on the device. The three terms of loss_functions.helmholtz_pml
+# as one [3] tensor (diff_constraint_on, diff_constraint_off, data_term = 0); the backward recomputes from the
+# same inputs.
+_LIB.define("helmholtz_loss(Tensor x, Tensor pred, Tensor jac, Tensor hess, Tensor src, Tensor slowness, "
+            "Tensor wavenumber) -> Tensor")
+_LIB.define("helmholtz_loss_bwd(Tensor x, Tensor pred, Tensor jac, Tensor hess, Tensor src, Tensor slowness, "
+            "Tensor wavenumber, Tensor g) -> (Tensor, Tensor, Tensor)")
+
+HELMHOLTZ_TERMS = 3
+
+
+def _helmholtz_operands(x, pred, jac, hess, src, slowness, wavenumber):
+    """Contiguous operands of the Helmholtz loss ops, shapes checked (the kernels index by pred's shape)."""
+    if pred.dim() != 3 or pred.shape[-1] != 2:
+        raise RuntimeError(f"siren_mri_amd.helmholtz_loss: pred {tuple(pred.shape)} must be [B, N, 2] (one complex "
+                           "field as two output channels)")
+    b, n, _ = pred.shape
+    for name, t, shape in (("x", x, (b, n, 2)), ("jac", jac, (b, n, 2, 2)), ("hess", hess, (b, n, 2, 2, 2)),
+                           ("src", src, (b, n, 2)), ("slowness", slowness, (b, n, 2))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"siren_mri_amd.helmholtz_loss: {name} {tuple(t.shape)} must be {list(shape)}")
+    if wavenumber.numel() != 1:
+        raise RuntimeError(f"siren_mri_amd.helmholtz_loss: wavenumber {tuple(wavenumber.shape)} must be one element")
+    for name, t in (("x", x), ("pred", pred), ("jac", jac), ("hess", hess), ("src", src), ("slowness", slowness),
+                    ("wavenumber", wavenumber)):
+        if t.dtype != torch.float32 or t.device != pred.device:
+            raise RuntimeError(f"siren_mri_amd.helmholtz_loss: {name} must be float32 on {pred.device}")
+    return (b * n, n, x.contiguous(), pred.contiguous(), jac.contiguous(), hess.contiguous(), src.contiguous(),
+            slowness.contiguous(), wavenumber.contiguous())
+
+
+def _helmholtz_loss_cuda(x, pred, jac, hess, src, slowness, wavenumber):
+    rows, n, *ops = _helmholtz_operands(x, pred, jac, hess, src, slowness, wavenumber)
+    out = torch.empty(HELMHOLTZ_TERMS, dtype=torch.float32, device=pred.device)
+    ws = _native.sse_workspace(pred.device)
+    rc = _native.lib().siren_helmholtz_loss_forward(*(t.data_ptr() for t in ops), rows, n, out.data_ptr(),
+                                                    ws.data_ptr(), ws.numel(), _native.stream_handle(pred.device))
+    _native.check(rc, "siren_helmholtz_loss_forward")
+    return out
+
+
+def _helmholtz_loss_bwd_cuda(x, pred, jac, hess, src, slowness, wavenumber, g):
+    rows, n, *ops = _helmholtz_operands(x, pred, jac, hess, src, slowness, wavenumber)
+    if g.numel() != HELMHOLTZ_TERMS or g.device != pred.device:
+        raise RuntimeError(f"siren_mri_amd.helmholtz_loss_bwd: g must be {HELMHOLTZ_TERMS} elements on the "
+                           "prediction's device")
+    g3 = _g32(g)
+    dpred, djac, dhess = torch.empty_like(ops[1]), torch.empty_like(ops[2]), torch.empty_like(ops[3])
+    rc = _native.lib().siren_helmholtz_loss_backward(*(t.data_ptr() for t in ops), rows, n, g3.data_ptr(),
+                                                     dpred.data_ptr(), djac.data_ptr(), dhess.data_ptr(),
+                                                     _native.stream_handle(pred.device))
+    _native.check(rc, "siren_helmholtz_loss_backward")
+    return dpred, djac, dhess
+
+
+class _HelmholtzLossAutograd(torch.autograd.Function):
+    """helmholtz_loss with helmholtz_loss_bwd as its backward: three differentiable inputs (pred, jac, hess), a
+    [3] upstream; the inputs are saved as they are (no residual is kept). x, src, slowness and wavenumber get
+    None: the path from x through the layer's coefficients is not provided (training discards that gradient,
+    model_in being a detached leaf)."""
+
+    @staticmethod
+    def forward(ctx, x, pred, jac, hess, src, slowness, wavenumber):
+        with torch._C._AutoDispatchBelowAutograd():
+            terms = torch.ops.siren_mri_amd.helmholtz_loss(x, pred, jac, hess, src, slowness, wavenumber)
+        ctx.save_for_backward(x, pred, jac, hess, src, slowness, wavenumber)
+        ctx.set_materialize_grads(False)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 7
+        if torch.is_grad_enabled():
+            raise RuntimeError("siren_mri_amd: double backward through the native Helmholtz loss is not provided; run "
+                               "it on the expression path (siren_mri_amd.loss_functions.set_helmholtz_loss_native(False))")
+        dpred, djac, dhess = torch.ops.siren_mri_amd.helmholtz_loss_bwd(*ctx.saved_tensors, g)
+        return None, dpred, djac, dhess, None, None, None
+
+
+_LIB.impl("helmholtz_loss", _helmholtz_loss_cuda, "CUDA")
+_LIB.impl("helmholtz_loss_bwd", _helmholtz_loss_bwd_cuda, "CUDA")
+_LIB.impl("helmholtz_loss", _HelmholtzLossAutograd.apply, "Autograd")
+torch.library.register_fake("siren_mri_amd::helmholtz_loss", lambda x, pred, jac, hess, src, slowness, wavenumber:
+                            pred.new_empty((HELMHOLTZ_TERMS,)), lib=_LIB)
+torch.library.register_fake("siren_mri_amd::helmholtz_loss_bwd", lambda x, pred, jac, hess, src, slowness, wavenumber, g:
+                            (torch.empty_like(pred), torch.empty_like(jac), torch.empty_like(hess)), lib=_LIB)

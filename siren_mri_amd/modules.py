@@ -4,7 +4,7 @@ Same class names, constructor signatures, parameter names and init RNG order as:
   BatchLinear      modules.py:11-27      Sine           modules.py:30-38
   FCBlock          modules.py:40-119     SingleBVPNet   modules.py:122-170
   ImageDownsampling modules.py:192-223   ConvImgEncoder modules.py:340-380 (+ Conv2dResBlock :433-450)
-  init functions   modules.py:600-654
+  init functions   modules.py:600-654    compl_conj / compl_div / compl_mul  modules.py:657-692
 so `state_dict`s and HyperNetwork parameter dicts interoperate with the reference.
 
 What changes is where the work runs: an FCBlock with nonlinearity='sine' executes its whole
@@ -413,3 +413,29 @@ class ConvImgEncoder(nn.Module):
         o = self.relu(self.conv_theta(I))
         o = self.cnn(o)
         return self.fc(self.relu_2(o).view(o.shape[0], self.hidden_size, -1)).squeeze(-1)
+
+
+# ------------------------------------------------------------------ complex operators (modules.py:657-692)
+# A tensor whose last dimension interleaves real and imaginary parts (re0, im0, re1, im1, ...), any even
+# channel count. Out of place: the results are built by stacking, not by writing slices of a new tensor.
+def _compl_join(re, im):
+    return torch.stack((re, im), dim=-1).flatten(-2)
+
+
+def compl_conj(x):
+    """conj(x)."""
+    return _compl_join(x[..., ::2], -x[..., 1::2])
+
+
+def compl_div(x, y):
+    """x / y."""
+    a, b, c, d = x[..., ::2], x[..., 1::2], y[..., ::2], y[..., 1::2]
+    den = c ** 2 + d ** 2
+    return _compl_join((a * c + b * d) / den, (b * c - a * d) / den)
+
+
+def compl_mul(x, y):
+    """x y, in the reference's three-multiplication form."""
+    a, b, c, d = x[..., ::2], x[..., 1::2], y[..., ::2], y[..., 1::2]
+    ac, bd = a * c, b * d
+    return _compl_join(ac - bd, (a + b) * (c + d) - ac - bd)
